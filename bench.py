@@ -22,7 +22,7 @@ Metric (BASELINE.json): Mray/s (primary + 1 bounce) at 1920x1080 on the syntheti
               ranks instead (torch.distributed.run, 127.0.0.1).  Both print the same metric string and "scaling": "strong".
               --shard samples (explicit, never under the headline metric string): every rank renders WHOLE frames for the sample indices rank,
               rank + N, ... (idkptSetSampleSequence); per-GPU work is fixed -> "weak"; a secondary mode for hosts that want samples per second.
-  roofline  = traversal kernel (k_trace2), fixed denominators from /opt/skills/guides/MI355X_MICROARCH.md.  achieved = algorithmic bytes (64 B per
+  roofline  = traversal kernel (k_trace2), fixed denominators from the MI355X microarchitecture guide.  achieved = algorithmic bytes (64 B per
               node-pair visit + 48 B per triangle test + 72 B per traversed ray, exact visit counts from the counting build) / HIP-event time of
               its launches in the timed region.  `frac` = achieved / 34.5 TB/s (aggregate L2, `bound: "l2"`): the 110 MB working set lives in L2 +
               Infinity Cache, so HBM does not bind and the algorithmic rate can exceed 8 TB/s — both HBM fractions (algorithmic, and from the
@@ -31,6 +31,13 @@ Metric (BASELINE.json): Mray/s (primary + 1 bounce) at 1920x1080 on the syntheti
               `traffic` and `pmc` are measured for THIS run: the timed region is re-executed under rocprofv3 --pmc (separate passes for
               FETCH_SIZE, WRITE_SIZE and the L2/L1 request counters; --kernel-trace only beside them) and the timed launches are averaged.
   cpu_baseline = the oracle's CPU port of the same path (all host cores, OpenMP), scene and threads kept warm, on a bounded sample.
+  plain run = what the headline figure needs and nothing else: set-up, --warmup steps, an untimed pre-roll (1 s of rehearsals of the timed
+              region's first displayed frames, <= 2 x samples_in_flight steps each), ONE timed region of exactly --steps steps (--repeats sets more), the outputs
+              of its last step (--dump-outputs), the result line.  Everything else above — the counter pass and
+              traversed_mray_s, the roofline with its micro-benchmark and rocprofv3 passes, the N > 1 bit-for-bit self-test, the secondary
+              blocks and cpu_baseline — runs only with --full, which also times 7 or more repetitions and reports the median.
+  outputs   = --dump-outputs DIR: the displayed frame after the last timed step (what PathTracer.Result returns: H x W x RGBA float32) as
+              DIR/image.npy; beyond 60 MiB a fixed seeded sample of its pixels (image_sample.npy + their indices, image_sample_pixels.npy).
 """
 import argparse
 import json
@@ -47,19 +54,20 @@ os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # the host driver onl
 W, H = 1920, 1080
 N_TRIS = 1_000_000
 RAY_DEPTH = 2
-HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBS = 8000.0          # MI355X microarchitecture guide: HBM3E 8.0 TB/s spec
 L2_PEAK_GBS = 34500.0          # same guide, "L2 (per XCD)": 4 MiB per XCD, ~34.5 TB/s aggregate
 NODE_PAIR_BYTES, TRI_BYTES, RAY_BYTES = 64, 48, 72     # node pair; triVerts entry; 48 B ray record + 4 B list entry + 20 B hit record
+PREROLL_S = 1.0                # untimed rehearsals of the timed region before it is timed (seconds, at least)
 
 
 def self_launch(args):
-    """`python bench.py --gpus N` without a launcher: become `python -m torch.distributed.run ... bench.py <same flags>`."""
+    """`python bench.py --gpus N --spawn` without a launcher: run `python -m torch.distributed.run ... bench.py <same flags>` as a child process and exit with its status."""
     import socket
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.abspath(__file__)] + sys.argv[1:]
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    os.execv(sys.executable, cmd)
+    sys.exit(subprocess.call(cmd))
 
 
 def view_camera(S, view, w, h):
@@ -74,11 +82,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64)
     ap.add_argument("--warmup", type=int, default=32)
-    ap.add_argument("--repeats", type=int, default=0, help="the timed region of --steps steps is repeated this often; the median repetition is reported.  0 (default): 7, "
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline figure: the counter pass (exact visit counts, traversed_mray_s), the roofline (micro-benchmark, "
+                    "rocprofv3 --pmc passes), the N > 1 self-test against one device, the secondary blocks, cpu_baseline, and the median of several repetitions of the timed region.  Off (default): a lean run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step computed (the displayed frame, H x W x RGBA float32) as DIR/image.npy (a fixed seeded sample of its pixels beyond 60 MiB)")
+    ap.add_argument("--repeats", type=int, default=0, help="the timed region of --steps steps is repeated this often; the median repetition is reported.  0 (default): once; with --full 7, "
                     "or as many as it takes to time >= 150 ms in total (at most 25): a region of a few milliseconds (--steps 20) is shorter than the GPU's clock ramp after the idle gap between regions")
     ap.add_argument("--tris", type=int, default=N_TRIS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the single-frame and interior-view measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the single-frame, interior-view and other secondary measurements")
     ap.add_argument("--view", choices=["headline", "interior"], default="headline", help="headline = BASELINE.json configs[2]; interior = camera inside the soup (secondary)")
     ap.add_argument("--scene", choices=["soup", "atrium"], default="soup", help="soup = BASELINE.json configs[2] (headline); atrium = procedural Sponza-class hall of --tris triangles, camera inside (secondary)")
     ap.add_argument("--depth", type=int, default=RAY_DEPTH, help="RayDepth (headline = 2); other values are secondary-table runs")
@@ -89,7 +100,7 @@ def main():
     ap.add_argument("--interactive", type=int, default=0, metavar="F", help="secondary mode: every step is a NEW frame (own camera, own image, ResetAccumulation semantics) with F frames in flight through the frame ring; every finished frame is exchanged when N > 1")
     ap.add_argument("--spawn", action="store_true", help="--gpus N without a launcher: start N processes (torch.distributed.run, one rank per GPU, RCCL) instead of the default ONE process driving ONE multi-device context (idkptCreate(deviceCount = N))")
     ap.add_argument("--shard", choices=["rows", "samples"], default="rows", help="one process per GPU (torch.distributed launch) only.  rows (default): the frame's rows are dealt over the ranks (bit-identical to one GPU, strong scaling: BASELINE.json's metric).  samples: every rank renders WHOLE frames for its own sample indices (idkptSetSampleSequence(rank, N)), one all-reduce per displayed frame, weak scaling — a secondary mode, never reported under the headline metric string")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc passes that measure roofline.traffic / roofline.pmc for this run (N = 1 only)")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the rocprofv3 --pmc passes that measure roofline.traffic / roofline.pmc for this run (N = 1 only)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)   # internal: the re-execution of the timed region under rocprofv3
     ap.add_argument("--cpu-build", action="store_true", help="build the BLAS entirely on the host (libidkbvh) instead of running the SweepSAH core on the GPU; the result is the same bytes")
     ap.add_argument("--batch", type=int, default=32, help="samples per GPU-frame-equivalent the library may defer and trace together (idkptSetMaxBatch; results are bit-identical); multiplied by the GPU count because each rank only holds 1/N of every frame, capped at 256")
@@ -188,11 +199,13 @@ def main():
         if step_no[0] % B == 0:
             finish_frame()
 
-    # ---- untimed counter pass over one displayed frame (B samples, one at a time): exact cumulative P (node-pair visits),
-    #      T (triangle tests), traversed rays and traced rays after each sample index of this rank's rows
-    cum = counter_pass(pt, B, depth)
+    full_run = args.full
     q, rem = divmod(args.steps, B)
-    pairs, tri_tests, traversed, rays_expected = (q * cum[B][i] + cum[rem][i] for i in range(4))   # per repetition
+    if full_run:
+        # ---- untimed counter pass over one displayed frame (B samples, one at a time): exact cumulative P (node-pair visits),
+        #      T (triangle tests), traversed rays and traced rays after each sample index of this rank's rows
+        cum = counter_pass(pt, B, depth)
+        pairs, tri_tests, traversed, rays_expected = (q * cum[B][i] + cum[rem][i] for i in range(4))   # per repetition
 
     pt.set_max_batch(B)
     step_no[0] = 0
@@ -200,9 +213,25 @@ def main():
         step()
     if step_no[0] % B:
         finish_frame()
+    # untimed pre-roll: a timed region that follows a short warm-up on a GPU that has not been busy runs slower than the steady state
+    # (profiles/r06_bench_line_driver_cmd.json: the first repetition 7.49 ms, then 6.59, then 6.4 ms).  Rehearsals of the region's first displayed
+    # frames (at most 2 B steps each, the same launch schedule) for PREROLL_S seconds, at least three; the ranks agree on when to stop.
+    t_pre, n_pre = time.perf_counter(), 0
+    while True:
+        step_no[0] = 0
+        for _ in range(min(args.steps, 2 * B)):
+            step()
+        if step_no[0] % B:
+            finish_frame()
+        pt.synchronize(); n_pre += 1
+        more = n_pre < 3 or time.perf_counter() - t_pre < PREROLL_S
+        if world > 1:
+            flag = torch.tensor([1.0 if more else 0.0], dtype=torch.float64, device=device); dist.all_reduce(flag, op=dist.ReduceOp.MAX); more = flag.item() > 0.0
+        if not more:
+            break
     pt.synchronize(); pt.reset_stats(); pt.enable_timing(True)
-    repeat_s, rays_rank = [], 0
-    want_reps = args.repeats if args.repeats > 0 else 7
+    repeat_s = []
+    want_reps = args.repeats if args.repeats > 0 else (7 if full_run else 1)
     while len(repeat_s) < want_reps:
         step_no[0] = 0
         if world > 1:
@@ -222,13 +251,17 @@ def main():
         if world > 1:
             dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         repeat_s.append(tmax.item())
-        if args.repeats <= 0 and len(repeat_s) == 1:                      # (the same count on every rank: derived from the all-reduced time)
+        if full_run and args.repeats <= 0 and len(repeat_s) == 1:             # (the same count on every rank: derived from the all-reduced time)
             want_reps = int(min(25, max(7, -(-0.15 // max(repeat_s[0], 1e-6)))))
     args.repeats = len(repeat_s)
     st = pt.stats()
     pt.enable_timing(False)
     reps = len(repeat_s)
-    assert st["rays_traced"] == rays_expected * reps, (st["rays_traced"], rays_expected, reps)  # every step traced its complete sample (exact ray count)
+    if full_run:
+        assert st["rays_traced"] == rays_expected * reps, (st["rays_traced"], rays_expected, reps)  # every step traced its complete sample (exact ray count)
+    else:
+        rays_expected, traversed = st["rays_traced"] / reps, 0.0                 # (the repetitions are identical: every one restarts the displayed frame)
+    dumped = dump_outputs(args.dump_outputs, final_image(pt, frame, world, torch), rank) if args.dump_outputs else None   # (every rank takes part in the exchange)
     rays_total = torch.tensor([float(rays_expected), float(traversed)], dtype=torch.float64, device=device)   # per repetition, this rank
     if world > 1:
         dist.all_reduce(rays_total, op=dist.ReduceOp.SUM)
@@ -238,7 +271,7 @@ def main():
     if world > 1:                                        # (a collective: every rank takes part, rank 0 reports)
         seen = torch.ones(1, dtype=torch.float64, device=device); dist.all_reduce(seen); ranks_counted = int(seen.item())
     selftest = None
-    if world * group > 1 and not sample_parallel and (depth <= 2 or ((args.exact_deep_paths or group > 1) and not args.sort)) and not args.pmc_child:   # (beyond RayDepth 2 the shards are exact with the count exchange: --exact-deep-paths, or one multi-device context)
+    if full_run and world * group > 1 and not sample_parallel and (depth <= 2 or ((args.exact_deep_paths or group > 1) and not args.sort)) and not args.pmc_child:   # (beyond RayDepth 2 the shards are exact with the count exchange: --exact-deep-paths, or one multi-device context)
         # the N-GPU frame against ONE device, bit for bit (what tools/scale_selftest.py checks, here on the bench's own frame): two accumulated samples, the sharded
         # frame exchanged as in the timed region, rank 0 renders the same two samples on its own device alone and compares
         try:
@@ -266,26 +299,29 @@ def main():
             "metric": "Mray/s (primary+1 bounce) at 1920x1080, 1M-tri scene" if headline else f"Mray/s (RayDepth {depth}) at {W}x{H}, {args.tris}-tri {args.scene} scene, {args.view if args.scene == 'soup' else 'interior'} view (secondary config{', sample-parallel: whole frames per GPU' if sample_parallel else ''}{', ' + str(world * group) + ' members SHARING ' + str(torch.cuda.device_count()) + ' visible GPU(s): control flow only, not an N-GPU number' if shared else ''})", "value": round(value, 2), "unit": "Mray/s",
             "n_gpus": world * group, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": "weak" if sample_parallel else "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "repeats": reps, "repeat_ms": [round(x * 1e3, 3) for x in repeat_s], "statistic": "median repetition of the timed region",
-            "traversed_mray_s": round(traversed_rep / dt / 1e6, 2),
+            "repeats": reps, "repeat_ms": [round(x * 1e3, 3) for x in repeat_s], "statistic": "median repetition of the timed region" if reps > 1 else "the timed region (--steps steps, once)",
+            **({"traversed_mray_s": round(traversed_rep / dt / 1e6, 2)} if full_run else {}),
             **transport_report(dist, world, group, pt, ranks_counted, one_device),
-            "config": {"headline_notes": ([f"{100.0 * (1.0 - traversed_rep / max(1.0, rays_rep)):.0f} % of the counted rays never enter the BVH: primary rays whose 8x8 tile or whose own root-box test misses the scene "
-                                          "(pre-classified sky; the same frame bit for bit) - the rate of the rays that do traverse is traversed_mray_s",
-                                          "defer_last=1: the continuation of the last bounce (next direction, throughput, queue) is produced on demand, not every frame - eager_last_bounce is the rate without it",
-                                          f"{B} samples in flight per launch - single_frame is the rate of a host that synchronises after every frame (SURVEY 8(d)'s protocol)"] if args.scene == "soup" and args.view == "headline" else None),
+            "config": {**({"headline_notes": ([f"{100.0 * (1.0 - traversed_rep / max(1.0, rays_rep)):.0f} % of the counted rays never enter the BVH: primary rays whose 8x8 tile or whose own root-box test misses the scene "
+                                               "(pre-classified sky; the same frame bit for bit) - the rate of the rays that do traverse is traversed_mray_s",
+                                               "defer_last=1: the continuation of the last bounce (next direction, throughput, queue) is produced on demand, not every frame - eager_last_bounce is the rate without it",
+                                               f"{B} samples in flight per launch - single_frame is the rate of a host that synchronises after every frame (SURVEY 8(d)'s protocol)"] if args.scene == "soup" and args.view == "headline" else None)} if full_run else {}),
                        "workload": (f"soup-{args.tris} (seeded random triangles, SweepSAH+PreSplit BVH, 1 BLAS), {W}x{H}, 1 spp, RayDepth {depth}, sort {'on' if args.sort else 'off'}, white sky, {view_txt}" if args.scene == "soup" else
                                      f"atrium-{args.tris} (procedural two-storey colonnaded hall, connected surfaces, {len(scene.blas_triangles)} BLAS triangles, 1 BLAS), {W}x{H}, 1 spp, RayDepth {depth}, sort {'on' if args.sort else 'off'}, white sky, camera inside looking down the hall"),
-                       "rays_per_step": int(rays_rep / args.steps), "traversed_rays_per_step": int(traversed_rep / args.steps),
+                       "rays_per_step": int(rays_rep / args.steps), **({"traversed_rays_per_step": int(traversed_rep / args.steps)} if full_run else {}),
                        "samples_in_flight": B, "displayed_frame": f"{B} accumulated samples, then exchange + ResetAccumulation",
                        "last_bounce": "every ray of the last bounce is traced and its radiance (sky on a miss; this scene has no emission, so hits add none) reaches the frame; the rest of that bounce's shading - new direction, throughput, Russian roulette, next queue: outputs the reference computes and nothing reads - is produced on demand (idkptDownloadRays / idkptDownloadAliveQueue / scene updates), bit-identical (DESIGN.md 4; option defer_last)", "sharding": ("one process, one multi-device context (idkptCreate(deviceCount = N)): scene replicated by peer copies, rows dealt round-robin in bands of 8 (beyond RayDepth 2 with the per-band alive-count exchange: exact at any depth), frame gathered on device 0" if group > 1 else (("sample-parallel: every rank renders whole frames for the sample indices rank, rank + N, ... (idkptSetSampleSequence); the displayed frame of N x samples_in_flight samples is the all-reduced mean of the ranks' accumulations; nothing is exchanged inside a frame" if sample_parallel else ("rows in bands of 8 round-robin over ranks + per-bounce exchange of the per-band alive counts enqueued on the render stream (idkptSetBandExchangeDevice: exact at any RayDepth, no host synchronisation) + all-gather" if args.exact_deep_paths else "rows round-robin over ranks + all-gather")) if world > 1 else "none")),
                        "bvh_build_s": round(build_s, 2), "blas_build_ms": blas_build_ms, "bvh_builder": builder_kind,
                        "blas_build_note": "blas_build_ms is the wall time of DeviceBuilder.build_blas as this script sees it: the device build (16 ms) + the download of nodes and triangles (23 ms together, profiles/r03_blas_build.txt) + numpy marshalling of 1 M triangles and the first call's allocations; untimed set-up, outside the metric",
                        "n_gpu": n_gpu_report(torch, dist, world, group, pt, st, B, depth, args, ranks_counted, selftest)},
-            "roofline": roofline(st, pairs * reps / group, tri_tests * reps / group, traversed * reps / group, args, world * group, B if rem == 0 else (rem if q == 0 else None), torch, device),
         }
+        if full_run:
+            out["roofline"] = roofline(st, pairs * reps / group, tri_tests * reps / group, traversed * reps / group, args, world * group, B if rem == 0 else (rem if q == 0 else None), torch, device)
+        if dumped:
+            out["outputs"] = dumped
         if args.pmc_child:
             out = {"pmc_child": True, "trace_launches": int(st["trace_launches"]), "ms_per_step": out["ms_per_step"]}
-        if world * group == 1 and not args.no_extras:
+        if full_run and world * group == 1 and not args.no_extras:
             # the same timed region with the last bounce shaded eagerly (option defer_last 0: new direction, throughput, Russian roulette and next queue of the bounce after
             # which nothing is traced, every frame, as the reference does): what `value` would be without producing those unread outputs on demand (config.last_bounce)
             pt.set_option("defer_last", 0)
@@ -323,12 +359,43 @@ def main():
                 safe(pt.UploadScene, scene)
                 out["queries"] = safe(query_extras, S, pt, scene, cam)
             pt.UseTlas = 0; pt.SetCamera(cam); pt.RayDepth = depth; pt.set_max_batch(B)
-        if world * group == 1 and not args.no_cpu_baseline:
+        if full_run and world * group == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = safe(cpu_baseline, S, scene, depth, args.view)
         print(json.dumps(out), flush=True)
     r.pt.Dispose()
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 60 << 20          # --dump-outputs: at most this many bytes of arrays (beyond: a fixed seeded sample of the pixels)
+
+
+def final_image(pt, frame, world, torch):
+    """The displayed frame after the last timed step, as a caller receives it: (H, W, 4) float32 RGBA.  N ranks: the exchanged frame (a collective: every rank calls it)."""
+    if world > 1:
+        full = frame.gather(); torch.cuda.synchronize()
+        return full.cpu().numpy()
+    return pt.Result
+
+
+def dump_outputs(out_dir, image, rank=0):
+    """--dump-outputs: DIR/image.npy (float32), or beyond DUMP_BYTES a fixed seeded sample of its pixels (image_sample.npy) with their row-major pixel indices
+    (image_sample_pixels.npy, float64).  Rank 0 writes; returns the names written (None on other ranks)."""
+    import numpy as np
+    if rank != 0:
+        return None
+    os.makedirs(out_dir, exist_ok=True)
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    if img.nbytes <= DUMP_BYTES:
+        arrays = {"image": img}
+    else:
+        px = img.reshape(-1, img.shape[-1])
+        k = DUMP_BYTES // (px.shape[1] * 4 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(len(px), size=k, replace=False))
+        arrays = {"image_sample": px[idx], "image_sample_pixels": idx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": [n + ".npy" for n in arrays]}
 
 
 def safe(fn, *a, **k):
@@ -791,10 +858,11 @@ def interactive(args, r, frame, pt, world, rank, device, scene, build_s, dist, t
     F = max(1, min(64, args.interactive))
     pt.SetFrameRing(2 * F); pt.set_max_batch(F)
     cams = [S.Camera(W, H, position=(2.0 * math.sin(0.02 * k), 1.0 * math.sin(0.013 * k), 25.0)) for k in range(64)]
-    state = {"k": 0, "first": None}
+    state = {"k": 0, "first": None, "last": None}
 
     def step():
         slot = pt.BeginFrame(); pt.SetCamera(cams[state["k"] % len(cams)]); pt.Compute()
+        state["last"] = slot
         if state["k"] % F == 0:
             state["first"] = slot
         state["k"] += 1
@@ -816,6 +884,13 @@ def interactive(args, r, frame, pt, world, rank, device, scene, build_s, dist, t
         dist.barrier()
     dt = time.perf_counter() - t0
     st = pt.stats()
+    dumped = None
+    if args.dump_outputs:                                           # the last frame of the timed steps (the last of the last exchanged group when N > 1)
+        if frame is not None:
+            img = frame.gather_frames(state["first"], F)[-1]; torch.cuda.synchronize(); img = img.cpu().numpy()
+        else:
+            img = pt.FrameResult(state["last"])
+        dumped = dump_outputs(args.dump_outputs, img, rank)
     rays = torch.tensor([float(st["rays_traced"])], dtype=torch.float64, device=device); tmax = torch.tensor([dt], dtype=torch.float64, device=device)
     if world > 1:
         dist.all_reduce(rays, op=dist.ReduceOp.SUM); dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -825,7 +900,8 @@ def interactive(args, r, frame, pt, world, rank, device, scene, build_s, dist, t
                           "n_gpus": world, "steps": steps, "warmup": args.warmup, "ms_per_step": round(dt / steps * 1e3, 4), "higher_is_better": True, "scaling": "strong",
                           "vs_baseline": None, "dtype": "f32", "data": "synthetic",
                           "config": {"workload": f"soup-{args.tris}, {W}x{H}, 1 spp, RayDepth {args.depth}, every frame its own camera and image", "frames_in_flight": F,
-                                     "frame_latency_ms": round(F * dt / steps * 1e3, 3), "exchange": "all-gather of every finished frame's row shards, once per F frames" if world > 1 else "none"}}), flush=True)
+                                     "frame_latency_ms": round(F * dt / steps * 1e3, 3), "exchange": "all-gather of every finished frame's row shards, once per F frames" if world > 1 else "none"},
+                          **({"outputs": dumped} if dumped else {})}), flush=True)
     r.pt.Dispose()
     if world > 1:
         dist.destroy_process_group()

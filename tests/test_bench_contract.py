@@ -51,3 +51,34 @@ def test_without_a_gpu_every_start_refuses_in_one_line():
         assert r.returncode != 0
         assert "bench.py needs a GPU" in (r.stderr + r.stdout), (cmd, r.stderr[-800:])
         assert "Traceback" not in r.stderr.split("bench.py needs a GPU")[0][-2000:], r.stderr[-1500:]
+
+
+def test_options_of_the_lean_and_the_full_run():
+    r = subprocess.run([sys.executable, "bench.py", "--help"], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0
+    assert "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
+def test_dump_outputs_whole_image_and_seeded_sample(tmp_path):
+    import numpy as np
+    b = _bench()
+    small = np.random.default_rng(5).random((27, 48, 4), dtype=np.float32)
+    got = b.dump_outputs(str(tmp_path / "a"), small)
+    assert got["files"] == ["image.npy"]
+    assert np.load(tmp_path / "a" / "image.npy").tobytes() == small.tobytes()
+    assert b.dump_outputs(str(tmp_path / "x"), small, rank=1) is None and not (tmp_path / "x").exists()
+    # beyond the budget: a fixed seeded sample of the pixels, with their indices, within 64 MB in all
+    h, w = 2160, 2048
+    big = np.arange(h * w * 4, dtype=np.float32).reshape(h, w, 4)
+    assert big.nbytes > b.DUMP_BYTES
+    for d in ("b", "c"):
+        got = b.dump_outputs(str(tmp_path / d), big)
+        assert sorted(got["files"]) == ["image_sample.npy", "image_sample_pixels.npy"]
+    total = sum(os.path.getsize(tmp_path / "b" / f) for f in got["files"])
+    assert total <= 64 * 1000 * 1000
+    px = np.load(tmp_path / "b" / "image_sample.npy"); idx = np.load(tmp_path / "b" / "image_sample_pixels.npy")
+    assert px.dtype == np.float32 and idx.dtype == np.float64 and len(px) == len(idx) > 0
+    assert np.all(np.diff(idx) > 0) and idx[-1] < h * w
+    assert np.array_equal(px, big.reshape(-1, 4)[idx.astype(np.int64)])
+    for f in got["files"]:
+        assert (tmp_path / "b" / f).read_bytes() == (tmp_path / "c" / f).read_bytes()      # the same sample every time

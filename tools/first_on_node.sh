@@ -2,7 +2,7 @@
 # First run on a real multi-GPU node (the build box has one GPU: DESIGN.md 6 "what has run where").  In order, stopping at the first failure:
 #   1. tools/scale_selftest.py, one process / one multi-device context (idkptCreate(N): peer matrix, RCCL transport, N members == 1 device bit for bit)
 #   2. tools/scale_selftest.py, one process per GPU over RCCL (rank -> device, ranks seen, sharded frame == 1 device bit for bit)
-#   3. bench.py --gpus N --steps 20 --warmup 5 as the driver launches it (one rank per GPU), then as ONE process driving one N-device context
+#   3. bench.py --full --gpus N --steps 20 --warmup 5 as the driver launches it (one rank per GPU), then as ONE process driving one N-device context
 # and prints, per bench line: value, n_gpus, transport, rccl_ranks_seen, the per-rank launch sizes and the frame check (bits_equal).
 #   usage: tools/first_on_node.sh [N = visible GPUs] [port = 29541]
 set -u
@@ -34,10 +34,10 @@ PY
 }
 if [ "$N" -gt 1 ]; then
   echo "== bench.py, one rank per GPU (the driver's command)"
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port $((PORT + 1)) bench.py --gpus "$N" --steps 20 --warmup 5 > "$OUT/bench_ranks.json" 2> "$OUT/bench_ranks.err" || { tail -5 "$OUT/bench_ranks.err"; echo "== FAIL: bench.py under torch.distributed.run"; exit 1; }
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port $((PORT + 1)) bench.py --full --gpus "$N" --steps 20 --warmup 5 > "$OUT/bench_ranks.json" 2> "$OUT/bench_ranks.err" || { tail -5 "$OUT/bench_ranks.err"; echo "== FAIL: bench.py under torch.distributed.run"; exit 1; }
   summarise "$OUT/bench_ranks.json" || { echo "== FAIL: the sharded frame differs from one device"; exit 1; }
 fi
 echo "== bench.py, one process, one $N-device context"
-python bench.py --gpus "$N" --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_context.json" 2> "$OUT/bench_context.err" || { tail -5 "$OUT/bench_context.err"; echo "== FAIL: bench.py --gpus $N in one process"; exit 1; }
+python bench.py --full --gpus "$N" --steps 20 --warmup 5 --no-cpu-baseline > "$OUT/bench_context.json" 2> "$OUT/bench_context.err" || { tail -5 "$OUT/bench_context.err"; echo "== FAIL: bench.py --gpus $N in one process"; exit 1; }
 summarise "$OUT/bench_context.json" || { echo "== FAIL: the N-device context's frame differs from one device"; exit 1; }
 echo "== done"

@@ -4,7 +4,7 @@ TAG=${1:-r01}
 export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT; cd $GRAFT_REPO_ROOT
-CMD="python bench.py --steps 64 --warmup 32 --no-cpu-baseline"
+CMD="python bench.py --full --steps 64 --warmup 32 --no-cpu-baseline"
 timeout 200 $CMD > $OUT/bench_plain.json 2> $OUT/bench_plain.err
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o b -- $CMD > $OUT/bench_stats.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -o b -- $CMD > $OUT/bench_fetch.log 2>&1
