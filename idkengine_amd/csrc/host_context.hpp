@@ -59,7 +59,7 @@ struct DevOptions {
                                  // meshes 2.2x; 64 clusters at 10 / 20 / 30 % overlap 1.68x / 1.44x / 1.19x from outside, 1.30x / 0.88x / 0.85x from inside; soup-1M in 60 parts (37 %) 1.06x / 1.12x,
                                  // in 12 parts (72 %) 1.03x / 0.98x
     int instTlas = 8;            // k_trace_inst (kernels_trace_inst.hpp): scenes of at least this many BLAS instances rendered WITHOUT UseTlas (the reference's instance loop, its default) are walked
-                                 // through a TLAS the library builds for itself; rays whose result could depend on the loop's order are traced again by the exact loop.  0 = the loop only.
+                                 // through a TLAS the library builds for itself; rays whose result could depend on the loop's order are traced again by the exact loop.  0 = no own TLAS (inst_unify and inst_sieve still apply: walk_plan.hpp).
                                  // Measured (round 5, profiles/r05_instance_tlas.md): the atrium as 87 BLASes 453 -> 1 641 Mray/s (3.6x; one frame at a time 363 -> 1 029), 0.3 % of the
                                  // rays traced again.  Bit-identical hits either way (tests/test_gpu_inst_tlas.py, tools/fuzz_parity.py).
     int instTlasOverlap = 10;    // ... only where the instances' boxes overlap little: a random line through the scene meets at most this many PERCENT of them (k_tlas_build measures it).

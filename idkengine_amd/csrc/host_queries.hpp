@@ -10,11 +10,10 @@ static int query_frame(dev_ctx* ctx, Frame& f, size_t& ldsBytes, uint32_t& grid)
     f.g = ctx->st.Gpu; f.useTlas = ctx->st.UseTlas;
     f.stackCap = std::max(1, ctx->st.BlasStackSize > 0 ? ctx->st.BlasStackSize : ctx->sceneStack);
     f.tlasCap = std::min(TLAS_STACK_SIZE, std::max(1, ctx->tlasNeed));
-    ldsBytes = (size_t)(f.stackCap + 2 + (f.useTlas ? f.tlasCap : 0)) * WAVE * 4;   // + the dummy and the spare row of k_trace2's stack (kernels_trace.hpp)
-    if (ldsBytes > 64 * 1024) return fail(ctx, IDKPT_ERR_INVALID_ARGUMENT, "BlasStackSize too large for the LDS traversal stack");
-    int wavesPerCU = (int)std::min<size_t>(32, (160 * 1024) / std::max<size_t>(ldsBytes, 1));
-    grid = (uint32_t)(ctx->numCUs * std::max(1, wavesPerCU));
-    return IDKPT_OK;
+    int wavesPerCU = 1;
+    int rc = trace_lds(ctx, f, f.useTlas ? f.tlasCap : 0, 0, ldsBytes, wavesPerCU);
+    grid = (uint32_t)(ctx->numCUs * wavesPerCU);
+    return rc;
 }
 
 // issue only (H2D, kernel, D2H on the context's stream); the caller synchronises.  hits must stay valid until then.
@@ -29,8 +28,7 @@ static int32_t dev_TraceRaysIssue(dev_ctx* ctx, const idkpt_ray* rays, size_t co
     if (count == 0) return IDKPT_OK;
     HIPC(hipSetDevice(ctx->device));
     FLUSH_KEEP();
-    Frame f; size_t ldsBytes; uint32_t grid;
-    int rc = query_frame(ctx, f, ldsBytes, grid); if (rc) return rc;
+    Frame f; size_t ldsBytes; uint32_t grid; int rc = query_frame(ctx, f, ldsBytes, grid); if (rc) return rc;
     DScene s = make_dscene(ctx);
     hipStream_t st = ctx->stream;
     const idkpt_ray* dIn = rays; idkpt_hit* dOut = hits;
@@ -41,19 +39,9 @@ static int32_t dev_TraceRaysIssue(dev_ctx* ctx, const idkpt_ray* rays, size_t co
     }
     HIPC(ctx->qwork.ensure((WORK_WORDS + 128) * 4));                       // its own work-list counters: the frame's are reset by the frame's last kernel, not per batch
     uint32_t* work = ctx->qwork.as<uint32_t>();
-    const int lights = (flags & IDKPT_TRACE_LIGHTS) ? 1 : 0;
-    if (ctx->opt.queryScheduler && !f.g.DoDebugBVHTraversal) {
-        const bool anyHit = (flags & IDKPT_TRACE_ANY_HIT) != 0;
-        if (!anyHit && ctx->instanceCount > 1 && !f.useTlas) {   // closest hits of a several-instance scene without UseTlas: the exact loop with its instance sieve where a frame would use it or the own TLAS (kernels_trace_inst.hpp)
-            bool useT = false, useS = false;
-            rc = inst_tlas_prepare(ctx, &useT, &useS); if (rc) return rc;
-            if ((useT || useS) && ctx->instRecValid) {
-                f.instSieve = 1; s.instRec = (const float4*)ctx->instRec.as<float4>();
-                ldsBytes = (size_t)(f.stackCap + 2 + inst_tlas_rows(ctx)) * WAVE * 4;
-                if (ldsBytes > 64 * 1024) return fail(ctx, IDKPT_ERR_INVALID_ARGUMENT, "BlasStackSize too large for the LDS traversal stack");
-                grid = (uint32_t)(ctx->numCUs * std::max(1, (int)std::min<size_t>(32, (160 * 1024) / ldsBytes)));
-            }
-        }
+    const int lights = (flags & IDKPT_TRACE_LIGHTS) ? 1 : 0; const bool anyHit = (flags & IDKPT_TRACE_ANY_HIT) != 0;
+    TracePlan plan; rc = trace_plan(ctx, f, s, false, true, anyHit, plan); if (rc) return rc;   // (closest hits of a several-instance scene without UseTlas: the exact loop with its instance sieve where a frame would use it or a tree; its LDS rows and grid)
+    if (plan.walk != Walk::Generic) {
         // closest hit / any hit: k_trace2's persistent-wave scheduler (kernels_query.hpp): prepare (lights, root test, trace-ready records) -> k_trace2 -> Hit flags
         HIPC(ctx->queryRec.ensure(count * 64)); HIPC(ctx->queryList.ensure(count * 4));
         HIPC(hipMemsetAsync(work, 0, (WORK_WORDS + 128) * 4, st));
@@ -66,16 +54,14 @@ static int32_t dev_TraceRaysIssue(dev_ctx* ctx, const idkpt_ray* rays, size_t co
         hipLaunchKernelGGL(k_query_prepare, dim3(blocks), dim3(256), 0, st, s, f, dIn, dOut, (uint32_t)count, lights, anyHit ? 1 : 0, tr, ctx->queryList.as<uint32_t>(), listCount);
         RayBufs noRays = {nullptr, nullptr, nullptr, nullptr, nullptr};
         HitBufs qhits = {(float4*)dOut, ctx->hitCost.as<float>()};
-        const uint32_t g2 = std::min<uint32_t>(grid, std::max<uint32_t>(1u, (uint32_t)((count + 63) / 64)));
-        launch_trace2<true>(ctx, g2, ldsBytes, st, s, f, noRays, tr, qhits, (const uint32_t*)ctx->queryList.as<uint32_t>(), (const uint32_t*)listCount, work, (uint64_t*)(work + WORK_WORDS + 64) /* visit counters of queries do not count as the frame's */, false, 0, anyHit);
+        const uint32_t g2 = std::min<uint32_t>(plan.grid, std::max<uint32_t>(1u, (uint32_t)((count + 63) / 64)));
+        launch_trace2<true>(ctx, plan, g2, st, s, f, noRays, tr, qhits, (const uint32_t*)ctx->queryList.as<uint32_t>(), (const uint32_t*)listCount, work, (uint64_t*)(work + WORK_WORDS + 64) /* visit counters of queries do not count as the frame's */);
         hipLaunchKernelGGL(k_query_finish, dim3(blocks), dim3(256), 0, st, dIn, dOut, (const uint32_t*)ctx->queryList.as<uint32_t>(), (const uint32_t*)listCount);
-        HIPC(hipGetLastError());
-        if (!devicePtrs) HIPC(hipMemcpyAsync(hits, ctx->queryOut.p, count * sizeof(idkpt_hit), hipMemcpyDeviceToHost, st));
-        return IDKPT_OK;
+    } else {
+        HIPC(hipMemsetAsync(work, 0, 4, st));
+        if (anyHit) hipLaunchKernelGGL((k_trace_query<true>), dim3(grid), dim3(WAVE), ldsBytes, st, s, f, dIn, dOut, (uint32_t)count, lights, work);
+        else hipLaunchKernelGGL((k_trace_query<false>), dim3(grid), dim3(WAVE), ldsBytes, st, s, f, dIn, dOut, (uint32_t)count, lights, work);
     }
-    HIPC(hipMemsetAsync(work, 0, 4, st));
-    if (flags & IDKPT_TRACE_ANY_HIT) hipLaunchKernelGGL((k_trace_query<true>), dim3(grid), dim3(WAVE), ldsBytes, st, s, f, dIn, dOut, (uint32_t)count, lights, work);
-    else hipLaunchKernelGGL((k_trace_query<false>), dim3(grid), dim3(WAVE), ldsBytes, st, s, f, dIn, dOut, (uint32_t)count, lights, work);
     HIPC(hipGetLastError());
     if (!devicePtrs) HIPC(hipMemcpyAsync(hits, ctx->queryOut.p, count * sizeof(idkpt_hit), hipMemcpyDeviceToHost, st));
     return IDKPT_OK;
@@ -100,8 +86,7 @@ static int32_t dev_TraceShadows(dev_ctx* ctx, const idkpt_shadow_params* p, cons
     if (ctx->st.UseTlas && ctx->tlasCount == 0) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptTraceShadows: UseTlas set but no TLAS nodes uploaded");
     HIPC(hipSetDevice(ctx->device));
     FLUSH_KEEP();
-    Frame f; size_t ldsBytes; uint32_t grid;
-    int rc = query_frame(ctx, f, ldsBytes, grid); if (rc) return rc;
+    Frame f; size_t ldsBytes; uint32_t grid; int rc = query_frame(ctx, f, ldsBytes, grid); if (rc) return rc;
     DScene s = make_dscene(ctx);
     const size_t N = (size_t)p->Width * p->Height;
     hipStream_t st = ctx->stream;

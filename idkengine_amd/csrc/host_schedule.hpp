@@ -11,8 +11,8 @@ static DScene make_dscene(dev_ctx* ctx, const uint8_t* slots, bool multi)
     s.nodes = (const float4*)at(VB_NODES); s.tris = ctx->tris.as<uint4>(); s.triVerts = (const float4*)at(VB_TRIVERTS);
     s.descs = ctx->descs.as<GpuBlasDesc>(); s.instances = ctx->instances.as<GpuBlasInstance>(); s.instanceCount = ctx->instanceCount;
     s.tlas = (const float4*)at(VB_TLAS); s.tlasCount = ctx->tlasCount; s.vertices = (const uint4*)at(VB_VERTICES);
-    s.instRec = nullptr;        // (set for the batches that walk the library's own TLAS, flush_batch)
-    s.pairNodes = nullptr;      // (set for the batches whose one-BLAS launches take k_trace2's FAST node step, flush_batch)
+    s.instRec = nullptr;        // (set for the batches that walk the library's own TLAS or sieve the instances: trace_plan)
+    s.pairNodes = nullptr;      // (set for the batches whose one-BLAS launches take k_trace2's FAST node step: trace_plan)
     s.meshes = ctx->meshes.as<GpuMesh>(); s.materials = ctx->materials.as<GpuMaterial>(); s.xforms = (const float4*)at(VB_XFORMS);
     s.lights = ctx->lights.as<GpuLight>(); s.lightCount = ctx->lightCount; s.sky = ctx->sky.as<float4>(); s.skySize = ctx->skySize;
     s.textures = ctx->texDescs.as<TexDesc>(); s.textureCount = ctx->textureCount; s.srgbLut = ctx->srgbLut.as<float>();
@@ -24,9 +24,6 @@ static DScene make_dscene(dev_ctx* ctx) { return make_dscene(ctx, nullptr, false
 static DScene make_dscene_last(dev_ctx* ctx) { return make_dscene(ctx, ctx->lastSlots, ctx->lastMulti); }   // what the last launched batch read (finish_deferred, regeneration of culled rays)
 
 static float4* image_ptr(dev_ctx* ctx, int i, int slot) { return ctx->img[i].as<float4>() + (size_t)slot * ((size_t)ctx->W * ctx->rows); }
-
-// fast path = persistent while-while traversal (one BLAS, instance list or TLAS); only the debug traversal-cost view uses the general kernel
-static bool fast_path(dev_ctx* ctx) { return ctx->instanceCount >= 1 && !ctx->st.Gpu.DoDebugBVHTraversal && !ctx->opt.forceGeneric; }
 
 // One batch of B deferred samples: FirstHit -> [sort ->] NHit x (RayDepth-1) -> FinalDraw (PathTracer.cs:218-270), every
 // stage launched once for all B samples.  Sample k owns ray ids [k*Npad, k*Npad+N); alive queues are batch-wide but stay
@@ -54,9 +51,7 @@ static bool want_split(const dev_ctx* ctx, uint32_t prev, bool known, int sample
 {
     if (ctx->opt.split == 0) return false;
     if (ctx->opt.split >= 2) return true;
-    const uint64_t pixels = (uint64_t)ctx->W * ctx->rows * (uint64_t)std::max(1, samples);
-    const bool sparse = ctx->lastFast && ctx->lastBatch == samples && (uint64_t)ctx->hCounts[MAX_DEPTH_SLOTS - 1] * 2u < pixels;
-    return known && sparse && prev > 0u && prev < SPLIT_MAX_RAYS;
+    return known && sparse_view(ctx, samples) && prev > 0u && prev < SPLIT_MAX_RAYS;
 }
 // k_trace_fused: where a batch's two traversal launches are bound by their longest rays, not by their ray count (the same regime as the split)
 // (measured: it saves launches, not chain length — +5 % where one sparse frame is traced alone, a loss everywhere else: kernels_trace_fused.hpp)
@@ -200,41 +195,19 @@ static int flush_batch(dev_ctx* ctx)
     f.tlasCap = std::min(TLAS_STACK_SIZE, std::max(1, ctx->tlasNeed));
     f.grabUnitLog2 = std::min(24, std::max(6, ctx->opt.grabUnitLog2)); f.grabFixed = std::max(0, ctx->opt.grabFixed);   // work-list hand-out (kernels_trace.hpp)
     f.leafMin = ctx->opt.leafMin > 0 ? ctx->opt.leafMin : (B >= 4 ? 16 : 12);        // (measured: 16-20 with many samples in flight, 12 for a frame traced alone; tools/sweep_sched.py)
-    f.instTlas = 0;                                                           // the instance loop through the library's own TLAS (kernels_trace_inst.hpp): decided per batch, the rays' producers look at it too
-    if (fast_path(ctx)) { bool useT = false, useS = false; int rc = inst_tlas_prepare(ctx, &useT, &useS); if (rc) { ctx->pending.clear(); return rc; } f.instTlas = useT ? 1 : 0; f.instSieve = useS ? 1 : 0; }
-    if (fast_path(ctx) && !multiVer && pair_nodes_wanted(ctx)) { int rc = pair_nodes_prepare(ctx); if (rc) { ctx->pending.clear(); return rc; } if (ctx->pairValid) s.pairNodes = (const float4*)ctx->pairNodes.as<float4>(); }
-    if (f.instSieve) s.instRec = (const float4*)ctx->instRec.as<float4>();
-    if (f.instTlas) { s.tlas = (const float4*)ctx->itlas.as<float4>(); s.tlasCount = 2 * ctx->instanceCount - 1; s.instRec = (const float4*)ctx->instRec.as<float4>(); }   // (what the kernels of this batch see as "the TLAS": only the primary rays' pre-cull and k_trace_inst look at it)
-    size_t ldsBytes = (size_t)(f.stackCap + 2 + (f.useTlas ? f.tlasCap : ((f.instTlas || f.instSieve) ? inst_tlas_rows(ctx) : 0))) * WAVE * 4;   // + the dummy and the spare row of k_trace2's stack (kernels_trace.hpp)
-    ldsBytes += (size_t)std::max(0, ctx->opt.ldsPad);   // option "lds_pad": caps the waves per CU (occupancy experiments)
-    if (ldsBytes > 64 * 1024) { ctx->pending.clear(); return fail(ctx, IDKPT_ERR_INVALID_ARGUMENT, "BlasStackSize too large for the LDS traversal stack"); }
-    // persistent trace grid: as many 1-wave workgroups as the chip holds (32 waves/CU, limited by LDS)
-    int wavesPerCU = (int)std::min<size_t>(32, (160 * 1024) / std::max<size_t>(ldsBytes, 1));
-    wavesPerCU = std::max(1, wavesPerCU);
-    if (ctx->opt.traceWaves > 0) wavesPerCU = ctx->opt.traceWaves;   // option "trace_waves": one-wave workgroups per CU in the persistent grid
-    // (a launch never needs more waves than it can have rays: small frames would otherwise spend their time dispatching idle workgroups)
-    const uint32_t traceGrid = std::min<uint32_t>((uint32_t)(ctx->numCUs * wavesPerCU), std::max<uint32_t>(1u, (uint32_t)(((size_t)B * N + 63) / 64)));
+    const bool fast = fast_path(ctx);
+    // (not where the samples of a batch are different frames — their own cameras or scene versions: the same pixel is then not the same ray, and under scene versions not even the
+    // same node addresses; measured on the animated bench, 8 / 32 frames in flight: 3 291 / 3 716 -> 3 011 / 3 117 Mray/s)
+    f.genPixelMajor = (fast && ctx->opt.genPixelMajor > 0 && B >= ctx->opt.genPixelMajor && !f.tilePerSample) ? 1 : 0;
+    // how this batch is traced (host_launch.hpp trace_plan): walk, packets, fusion, LDS bytes and the persistent grid — as many 1-wave workgroups as the chip holds, but never more waves than the launch can have rays (small frames would spend their time dispatching idle workgroups)
+    TracePlan plan; { int rc = trace_plan(ctx, f, s, multiVer, false, false, plan); if (rc) { ctx->pending.clear(); return rc; } }
+    const size_t ldsBytes = plan.ldsBytes; const int wavesPerCU = plan.wavesPerCU; const bool fused = plan.fused;
+    const uint32_t traceGrid = std::min<uint32_t>(plan.grid, std::max<uint32_t>(1u, (uint32_t)(((size_t)B * N + 63) / 64)));
     const uint32_t midGrid = (ctx->opt.gridMidWaves > 0 && ctx->opt.traceWaves == 0) ? (uint32_t)(ctx->numCUs * std::min(wavesPerCU, ctx->opt.gridMidWaves)) : 0u;   // (an explicit trace_waves wins)
     f.gridRaysX4 = (uint32_t)std::max(0, ctx->opt.gridRaysX4); f.gridMid = midGrid; f.gridMidRays = GRID_MID_RAYS; f.splitMode = (ctx->opt.split == 3 ? 2 : 1) | (ctx->opt.splitDonor ? 4 : 0); f.poolMin = ctx->opt.poolMin; f.advMin = ctx->opt.advMin > 0 ? ctx->opt.advMin : (B >= 4 ? 8 : 1); f.splitPeek = ctx->opt.splitPeek;   // the same rules inside k_trace2, on the launch's actual ray count
     const bool debug = f.g.DoDebugBVHTraversal != 0;
     const uint32_t gridTotal = (total + 255) / 256;
-    const bool fast = fast_path(ctx);
-    if (fast && wide_wanted(ctx)) { int rc = wide_prepare(ctx); if (rc) { ctx->pending.clear(); return rc; } }
-    // (not where the samples of a batch are different frames — their own cameras or scene versions: the same pixel is then not the same ray, and under scene versions not even the
-    // same node addresses; measured on the animated bench, 8 / 32 frames in flight: 3 291 / 3 716 -> 3 011 / 3 117 Mray/s)
-    f.genPixelMajor = (fast && ctx->opt.genPixelMajor > 0 && B >= ctx->opt.genPixelMajor && !f.tilePerSample) ? 1 : 0;
-    // the primary launch as a packet launch (kernels_packet.hpp): one-BLAS scenes; by the kernel's own counters unless forced (host_launch.hpp packet_decide)
-    const bool packet = fast && !multiVer && !f.useTlas && packet_decide(ctx, f);
-    // one launch for FirstHit + the last NHit (kernels_trace_fused.hpp): RayDepth 2, one BLAS instance, the last bounce deferred (no AOVs, no debug view), nothing that looks at
-    // the primary hits or the visit counters, no per-bounce exchange with other contexts — and a launch small enough to be bound by its longest rays
-    const bool fused = fast && ctx->st.RayDepth == 2 && ctx->opt.deferLast != 0 && !f.outputAovs && !f.g.DoDebugBVHTraversal && !f.useTlas && ctx->instanceCount == 1 && !multiVer && !ctx->counters
-                       && !ctx->capturePrimary && !ctx->groupExchange && !ctx->exchangeFn && !ctx->bandExchangeFn && !ctx->bandExchangeDevFn && (ctx->opt.traceVariant == 0 || ctx->opt.traceVariant == 100)
-                       && !(packet && ctx->opt.packet >= 2)             // (a forced packet walk is the tests' setting: nothing else takes the primary launch)
-                       && !(wide_wanted(ctx) && ctx->opt.fused < 2)    // (the wide-node walk shortens the dependent chains the fused launch only stops paying launches for)
-                       && want_fused(ctx, ctx->hCounts[MAX_DEPTH_SLOTS - 1], ctx->lastFast && ctx->lastBatch == B, B);
-    f.packet = (packet && !fused) ? 1 : 0;
-    if (f.packet) { int rc = packet_prepare(ctx); if (rc) { ctx->pending.clear(); return rc; } }
-    f.hitsByRid = fused ? 1 : 0; f.shadeMin = ctx->opt.fusedShadeMin; f.scatterLog2 = ctx->opt.splitScatter;
+    f.shadeMin = ctx->opt.fusedShadeMin; f.scatterLog2 = ctx->opt.splitScatter;
     if (!fast && (B != 1 || multiVer)) { ctx->pending.clear(); return fail(ctx, IDKPT_ERR_UNKNOWN, "internal: generic path is never batched"); }
     unsigned long long* contMask = ctx->contMask.as<unsigned long long>();
     uint32_t* waveCounts = ctx->waveCounts.as<uint32_t>();
@@ -279,7 +252,7 @@ static int flush_batch(dev_ctx* ctx)
                 // FirstHit's traversal, its shading and the bounce's traversal in one persistent launch (kernels_trace_fused.hpp); the bounce's hits are stored per ray id
                 hipLaunchKernelGGL((k_trace_fused<32>), dim3(grid0), dim3(WAVE), ldsBytes, st, s, f, rays, tr, hits, (const uint32_t*)activeList, (const uint32_t*)activeCount, work + 0, ctx->contFlag.as<uint8_t>(), keysTmp, lean);
             } else
-            launch_trace2<true>(ctx, grid0, ldsBytes, st, s, f, rays, tr, hits, (const uint32_t*)activeList, (const uint32_t*)activeCount, work + 0, counters,
+            launch_trace2<true>(ctx, plan, grid0, st, s, f, rays, tr, hits, (const uint32_t*)activeList, (const uint32_t*)activeCount, work + 0, counters,
                                 want_split(ctx, ctx->hCounts[MAX_DEPTH_SLOTS - 1], ctx->lastFast && ctx->lastBatch == B, B), 0);
             TRACE_T1();
             if (ctx->capturePrimary) { HIPC(ctx->primHit.ensure((size_t)N * 16)); hipLaunchKernelGGL(k_capture_primary, dim3((N + 255) / 256), dim3(256), 0, st, hits, (size_t)(B - 1) * Npad, N, ctx->primHit.as<float4>()); }
@@ -394,10 +367,10 @@ static int flush_batch(dev_ctx* ctx)
         if (hintMul > 0 && ctx->lastBatch == B && ctx->hBases) gridj = small_launch_grid(traceGrid, ctx->hBases[(size_t)j * BS + B], hintMul, ctx->opt.gridRaysX4, midGrid);
         if (fast && pmBounce && j == 1) {   // the list k_shade_first wrote: ray ids, hits stored per ray id (the PRIMARY instantiations read exactly that)
             Frame ft = f; ft.hitsByRid = 0;
-            launch_trace2<true>(ctx, gridj, ldsBytes, st, s, ft, rays, tr, hits, (const uint32_t*)pmList, (const uint32_t*)pmCount, work + j, counters,
+            launch_trace2<true>(ctx, plan, gridj, st, s, ft, rays, tr, hits, (const uint32_t*)pmList, (const uint32_t*)pmCount, work + j, counters,
                                 want_split(ctx, ctx->hBases ? ctx->hBases[(size_t)j * BS + B] : 0u, ctx->lastFast && ctx->lastBatch == B && ctx->hBases != nullptr, B), j);
         } else
-        if (fast) launch_trace2<false>(ctx, gridj, ldsBytes, st, s, f, rays, tr, hits, (const uint32_t*)q, cnt, work + j, counters,
+        if (fast) launch_trace2<false>(ctx, plan, gridj, st, s, f, rays, tr, hits, (const uint32_t*)q, cnt, work + j, counters,
                                        want_split(ctx, ctx->hBases ? ctx->hBases[(size_t)j * BS + B] : 0u, ctx->lastFast && ctx->lastBatch == B && ctx->hBases != nullptr, B), j);
         else {
             if (ctx->counters) hipLaunchKernelGGL((k_trace_queue<true>), dim3(traceGrid), dim3(WAVE), ldsBytes, st, s, f, rays, hits, (const uint32_t*)q, cnt, work + j, counters);

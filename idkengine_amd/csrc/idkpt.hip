@@ -36,6 +36,7 @@ using namespace ptd;
 
 // =================================================================================================== host side (one file per concern, in dependency order)
 #include "host_context.hpp"
+#include "walk_plan.hpp"
 #include "host_launch.hpp"
 #include "host_frame.hpp"
 #include "host_scene.hpp"

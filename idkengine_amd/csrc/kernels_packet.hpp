@@ -6,7 +6,7 @@
 // instruction issue at 39 of 64 live lanes per step with 45 scalar instructions of bookkeeping on top of the 62 vector ones.  Where the 64 rays of a wave want the SAME nodes that is
 // 64 copies of one walk.  tools/packet_sim.cpp (CPU model, the bench scenes at 1920x1080, 4 pixels x 16 samples per wave): a shared walk takes 0.66-0.70 x the wave steps of k_trace2
 // on the views where every pixel traverses (interior 153 vs 230 per 64 rays, atrium 35 vs 53) with 0.87-0.88 of the wave's rays live in a step — and 1.14-1.57 x on the headline
-// view, whose pixels are wider than its triangles (0.37-0.54 live): the host decides per view from what the kernel itself counts (host_launch.hpp: packet_decide).
+// view, whose pixels are wider than its triangles (0.37-0.54 live): the host decides per view from what the kernel itself counts (walk_plan.hpp: packet_vote, host_launch.hpp: packet_decide).
 //
 // WHAT.  One wave = one packet of 64 consecutive list entries; no refill inside a packet.
 //   * the walk's state is wave-uniform: the current node pair and the 64-bit mask of lanes it is live for in SGPRs, the stack in three VGPRs (lane k holds entry k: node, mask lo / hi;
@@ -26,7 +26,7 @@
 //     inside T * WINDOW (1 + 2^-16), if its best hit is a MARKED triangle (a PreSplit fragment: not contained in its leaf box; which copy the reference reports depends on its order;
 //     InstTlasBufs::marks, k_mark_triangles), if a tested triangle violates the argument's one ASSUMPTION (a hit more than 3 * 2^-16 in front of its own leaf box's entry), if one of
 //     its box tests failed by less than 2^-20 relative (NEAR_MISS), if a component of 1/dir is not finite (NaN slabs), or if the packet's stack overflowed (64 entries).
-//   Not covered, as there: the reference's visit counters (DoDebugBVHTraversal, the counting build), any-hit queries, scene versions, several instances — those keep k_trace2.
+//   Not covered, as there: the reference's visit counters (DoDebugBVHTraversal, the counting build), any-hit queries, scene versions, several instances that are not one space (a same-space scene's unified tree is walked as packets too: UNI) — those keep their walk (walk_plan.hpp).
 #pragma once
 
 struct PacketBufs {

@@ -434,13 +434,13 @@ IDKPT_API int32_t idkptEnableTiming(idkpt_ctx* ctx, int32_t enable);
  *     "pool_min"         >= 0 (12*)  (ray, triangle) pairs a wave must have parked before they are pooled
  *     "wide"             0* / 1      k_trace_wide: closest hits over the derived 4-wide nodes, unvouched rays re-traced by k_trace2 (csrc/wide_nodes.hpp; profiles/r05_wide_nodes.md)
  *     "wide_cap"         0* / 4-96   rows of its per-lane stack (0 = 24)        "wide_count" 0* / 1   count its node / leaf-record / triangle fetches (idkpt_stats.Wide*)
- *     "packet"           0-2 (1*)    k_trace_packet: the primary launch of a one-BLAS scene as wave-uniform packets (one shared walk per wave of 64 consecutive work-list entries, node pairs and triangles
- *                                    through the scalar cache), unvouched rays re-traced by k_trace2 (idkpt_stats.Packet*; csrc/kernels_packet.hpp, profiles/r06_packet.md): 0 never, 1 pixel-major lists
- *                                    (batches of >= gen_pixel_major samples) while the kernel's own counters show the wave's rays wanting the same nodes, 2 every primary launch of a one-BLAS scene
+ *     "packet"           0-2 (1*)    k_trace_packet: the primary launch of a one-BLAS scene — or of a same-space scene on its unified tree ("inst_unify") — as wave-uniform packets (one shared walk per wave of 64 consecutive work-list entries, node pairs and triangles
+ *                                    through the scalar cache), unvouched rays re-traced by k_trace2 / the exact instance loop (idkpt_stats.Packet*; csrc/kernels_packet.hpp, profiles/r06_packet.md): 0 never, 1 pixel-major lists
+ *                                    (batches of >= gen_pixel_major samples) while the kernel's own counters show the wave's rays wanting the same nodes, 2 every primary launch of such a scene
  *     "packet_min_live"  0-100 (60*) ... percent of a wave's lanes live in an average node step below which the automatic choice turns the packet walk off      "packet_waves" 0* / 1-32   its waves per CU (0 = 28)
  *     "inst_tlas"        >= 0 (8*)   k_trace_inst: scenes of at least this many BLAS instances rendered WITHOUT UseTlas (the reference's instance loop, BVHIntersect.glsl:275-287) walk a
  *                                    TLAS the library builds for itself; rays whose hit could depend on the loop's order are traced again by the exact loop (idkpt_stats.InstTlasFlaggedRays;
- *                                    csrc/kernels_trace_inst.hpp, profiles/r05_instance_tlas.md).  0 = the loop only.  Not used with the counting build, DoDebugBVHTraversal, scene versions.
+ *                                    csrc/kernels_trace_inst.hpp, profiles/r05_instance_tlas.md).  0 = no own TLAS; scenes that "inst_unify" serves keep walking the unified tree (only inst_unify = 0 turns that off) and "inst_sieve" still sieves the loop.  Not used with the counting build, DoDebugBVHTraversal, scene versions.
  *     "inst_tlas_overlap" 0-100 (10*) ... only while a random line through the scene meets at most this many percent of the instances' boxes (measured on the device at every rebuild)
  *     "inst_braid"       >= 0 (0*)   ... and the tree's leaves are subtrees of the instances' BLASes (partial re-braiding, k_braid in csrc/kernels_scene.hpp: the entries with the largest boxes are opened into
  *                                    their node's children until the list has this many entries; scenes whose BLAS boxes nest).  0 = whole instances (measured: more entries lose, profiles/r06_braid.md)
