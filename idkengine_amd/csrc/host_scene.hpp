@@ -123,7 +123,7 @@ static int32_t dev_Destroy(dev_ctx* ctx)
     (void)hipSetDevice(ctx->device);
     ctx->pending.clear();
     (void)hipStreamSynchronize(ctx->stream);
-    DevBuf* all[] = {&ctx->srgbLut, &ctx->pmList, &ctx->pairNodes, &ctx->instRec, &ctx->entRec, &ctx->braidBuf, &ctx->unodes, &ctx->utlas, &ctx->uTabs, &ctx->uniBuf, &ctx->uniEntRec, &ctx->itlas, &ctx->imarks, &ctx->ichunks, &ctx->wnodes, &ctx->wleaf, &ctx->wids, &ctx->wpair, &ctx->wcounts, &ctx->wtotals, &ctx->nodes, &ctx->tris, &ctx->triVerts, &ctx->descs, &ctx->instances, &ctx->tlas, &ctx->parents, &ctx->leaves, &ctx->positions, &ctx->prevPositions, &ctx->vertices, &ctx->meshes,
+    DevBuf* all[] = {&ctx->srgbLut, &ctx->texStage, &ctx->pmList, &ctx->pairNodes, &ctx->instRec, &ctx->entRec, &ctx->braidBuf, &ctx->unodes, &ctx->utlas, &ctx->uTabs, &ctx->uniBuf, &ctx->uniEntRec, &ctx->itlas, &ctx->imarks, &ctx->ichunks, &ctx->wnodes, &ctx->wleaf, &ctx->wids, &ctx->wpair, &ctx->wcounts, &ctx->wtotals, &ctx->nodes, &ctx->tris, &ctx->triVerts, &ctx->descs, &ctx->instances, &ctx->tlas, &ctx->parents, &ctx->leaves, &ctx->positions, &ctx->prevPositions, &ctx->vertices, &ctx->meshes,
                      &ctx->materials, &ctx->xforms, &ctx->lights, &ctx->sky, &ctx->texDescs, &ctx->unskinned, &ctx->joints, &ctx->levelNodes, &ctx->tlasScratch, &ctx->queryIn, &ctx->queryOut, &ctx->queryRec, &ctx->queryList, &ctx->bandTab, &ctx->tileClass, &ctx->gbases, &ctx->camTab, &ctx->verTab, &ctx->trRec, &ctx->contFlag, &ctx->blockSums, &ctx->rayO, &ctx->rayT, &ctx->rayR, &ctx->aovA, &ctx->aovN, &ctx->hit,
                      &ctx->hitCost, &ctx->primHit, &ctx->queue[0], &ctx->queue[1], &ctx->keys[0], &ctx->keys[1], &ctx->keysTmp, &ctx->sortKeys, &ctx->sortVals, &ctx->contMask, &ctx->waveCounts,
                      &ctx->counts, &ctx->work, &ctx->qwork, &ctx->radSave, &ctx->deferCount, &ctx->sortHist, &ctx->counters64, &ctx->bases, &ctx->img[0], &ctx->img[1], &ctx->img[2]};
@@ -284,22 +284,65 @@ static int upload(dev_ctx* ctx, DevBuf& b, const void* src, size_t bytes)
 }
 
 // ---- texture table (idkpt_texture: include/idkpt.h) -----------------------------------------------------------------------------------------------------------------
-static size_t tex_texel_bytes(int32_t format) { return format == IDKPT_TEXFMT_RGBA32F ? 16 : 4; }
+// Formats >= IDKPT_TEXFMT_R8 are SOURCE formats: the host's bytes are staged on the device and one kernel (kernels_texture.hpp) expands them into the resident format the sampler reads.
+static int32_t tex_resident_format(int32_t format)
+{
+    switch (format) {
+    case IDKPT_TEXFMT_R8: case IDKPT_TEXFMT_RG8: case IDKPT_TEXFMT_BC7_RGBA: return IDKPT_TEXFMT_RGBA8;
+    case IDKPT_TEXFMT_R11G11B10F: case IDKPT_TEXFMT_BC4_R: case IDKPT_TEXFMT_BC5_RG: return IDKPT_TEXFMT_RGBA32F;
+    case IDKPT_TEXFMT_BC7_SRGBA: return IDKPT_TEXFMT_SRGB8_A8;
+    default: return format;
+    }
+}
+static bool tex_decoded(int32_t format) { return format >= IDKPT_TEXFMT_R8; }
+static size_t tex_texel_bytes(int32_t format) { return tex_resident_format(format) == IDKPT_TEXFMT_RGBA32F ? 16 : 4; }   // of the resident image
+static size_t tex_resident_bytes(const idkpt_texture& t) { return (size_t)t.width * t.height * tex_texel_bytes(t.format); }
+// bytes the host passes in idkpt_texture::rgba
+static size_t tex_source_bytes(const idkpt_texture& t)
+{
+    const size_t texels = (size_t)t.width * t.height, blocks = (size_t)((t.width + 3) / 4) * ((t.height + 3) / 4);
+    switch (t.format) {
+    case IDKPT_TEXFMT_R8: return texels;
+    case IDKPT_TEXFMT_RG8: return texels * 2;
+    case IDKPT_TEXFMT_R11G11B10F: return texels * 4;
+    case IDKPT_TEXFMT_BC4_R: return blocks * 8;
+    case IDKPT_TEXFMT_BC5_RG: case IDKPT_TEXFMT_BC7_RGBA: case IDKPT_TEXFMT_BC7_SRGBA: return blocks * 16;
+    default: return tex_resident_bytes(t);
+    }
+}
 static int tex_validate(dev_ctx* ctx, const idkpt_texture& t, const char* who)
 {
     if (!(t.width > 0 && t.height > 0 && t.rgba)) return fail(ctx, IDKPT_ERR_INVALID_ARGUMENT, std::string(who) + ": bad texture (size / data)");
-    if (!(t.wrapS >= 0 && t.wrapS <= 2 && t.wrapT >= 0 && t.wrapT <= 2 && t.magFilter >= 0 && t.magFilter <= 1 && t.format >= 0 && t.format <= 2))
+    if (!(t.wrapS >= 0 && t.wrapS <= 2 && t.wrapT >= 0 && t.wrapT <= 2 && t.magFilter >= 0 && t.magFilter <= 1 && t.format >= 0 && t.format <= IDKPT_TEXFMT_BC7_SRGBA))
         return fail(ctx, IDKPT_ERR_INVALID_ARGUMENT, std::string(who) + ": bad texture (wrapS / wrapT are enum idkpt_wrap, magFilter enum idkpt_filter, format enum idkpt_texture_format)");
     return IDKPT_OK;
 }
-static uint32_t tex_state(const idkpt_texture& t) { return (uint32_t)t.wrapS | ((uint32_t)t.wrapT << 2) | ((uint32_t)t.magFilter << 4) | ((uint32_t)t.format << 5); }
-// can a texel of this image be non-finite?  (k_shade_last's "no emission" shortcut: 0 x a texel is only 0 for a finite texel; 8-bit formats decode to [0, 1])
+static uint32_t tex_state(const idkpt_texture& t) { return (uint32_t)t.wrapS | ((uint32_t)t.wrapT << 2) | ((uint32_t)t.magFilter << 4) | ((uint32_t)tex_resident_format(t.format) << 5); }
+// can a texel of this image be non-finite?  (k_shade_last's "no emission" shortcut: 0 x a texel is only 0 for a finite texel; 8-bit formats decode to [0, 1], BC4 / BC5 too)
 static bool tex_all_finite(const idkpt_texture& t)
 {
+    if (t.format == IDKPT_TEXFMT_R11G11B10F) {                          // Inf / NaN: a field whose 5-bit exponent is 31
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(t.rgba); uint32_t bad = 0;
+        for (size_t k = 0, e = (size_t)t.width * t.height; k < e; k++) bad |= (uint32_t)(((w[k] >> 6) & 31u) == 31u) | (uint32_t)(((w[k] >> 17) & 31u) == 31u) | (uint32_t)((w[k] >> 27) == 31u);
+        return !bad;
+    }
     if (t.format != IDKPT_TEXFMT_RGBA32F) return true;
     const uint32_t* w = reinterpret_cast<const uint32_t*>(t.rgba); uint32_t bad = 0;
     for (size_t k = 0, e = (size_t)t.width * t.height * 4; k < e; k++) bad |= (uint32_t)((w[k] & 0x7f800000u) == 0x7f800000u);
     return !bad;
+}
+// the decode of one staged source image (formats >= IDKPT_TEXFMT_R8) into its resident image, queued on the context's stream
+static int tex_decode_launch(dev_ctx* ctx, const idkpt_texture& t, const void* staged, void* resident)
+{
+    const size_t texels = (size_t)t.width * t.height, blocks = (size_t)((t.width + 3) / 4) * ((t.height + 3) / 4);
+    if (t.format == IDKPT_TEXFMT_BC7_RGBA || t.format == IDKPT_TEXFMT_BC7_SRGBA)
+        hipLaunchKernelGGL(k_tex_decode_bc7, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, ctx->stream, (const uint4*)staged, (uint32_t*)resident, t.width, t.height);
+    else if (t.format == IDKPT_TEXFMT_BC4_R || t.format == IDKPT_TEXFMT_BC5_RG)
+        hipLaunchKernelGGL(k_tex_decode_rgtc, dim3((unsigned)((texels + 255) / 256)), dim3(256), 0, ctx->stream, (const uint64_t*)staged, (float4*)resident, t.width, t.height, t.format == IDKPT_TEXFMT_BC5_RG ? 1 : 0);
+    else
+        hipLaunchKernelGGL(k_tex_expand_linear, dim3((unsigned)((texels + 255) / 256)), dim3(256), 0, ctx->stream, (const uint8_t*)staged, resident, texels, (int)t.format);
+    HIPC(hipGetLastError());
+    return IDKPT_OK;
 }
 // the sRGB -> linear transfer function of GL 4.6 8.24 per byte value, evaluated in double and rounded once (the oracle makes the same table with the same expression)
 static int tex_srgb_lut(dev_ctx* ctx)
@@ -344,6 +387,8 @@ static int32_t dev_UploadScene(dev_ctx* ctx, const idkpt_scene_desc* sc)
     REQUIRE(sc->VertexPositions && sc->Vertices && sc->VertexCount > 0, "idkptUploadScene: vertices missing");
     REQUIRE(sc->Meshes && sc->MeshCount > 0 && sc->Materials && sc->MaterialCount > 0 && sc->MeshTransforms && sc->MeshTransformCount > 0, "idkptUploadScene: meshes/materials/transforms missing");
     REQUIRE(sc->LightCount >= 0 && sc->LightCount <= IDKPT_MAX_LIGHTS, "idkptUploadScene: more than 256 lights");
+    REQUIRE(sc->TextureCount >= 0 && (sc->TextureCount == 0 || sc->Textures), "idkptUploadScene: Textures missing");
+    for (int i = 0; i < sc->TextureCount; i++) { int trc = tex_validate(ctx, sc->Textures[i], "idkptUploadScene"); if (trc) return trc; }   // before anything of the resident scene changes
     // validate indices so that a bad host array cannot fault the GPU
     for (int i = 0; i < sc->BlasTriangleCount; i++) { const GpuBlasTriangle& t = sc->BlasTriangles[i]; REQUIRE(t.X < (uint32_t)sc->VertexCount && t.Y < (uint32_t)sc->VertexCount && t.Z < (uint32_t)sc->VertexCount && t.MeshId < (uint32_t)sc->MeshCount, "idkptUploadScene: BlasTriangle index out of range"); }
     for (int i = 0; i < sc->MeshCount; i++) REQUIRE(sc->Meshes[i].MaterialId >= 0 && sc->Meshes[i].MaterialId < sc->MaterialCount, "idkptUploadScene: Mesh.MaterialId out of range");
@@ -395,11 +440,22 @@ static int32_t dev_UploadScene(dev_ctx* ctx, const idkpt_scene_desc* sc)
     for (auto& t : ctx->texData) t.release();
     ctx->texData.clear(); ctx->texDims.clear(); ctx->texState.clear();
     if ((rc = tex_srgb_lut(ctx))) return rc;
+    {   // one staging allocation for the source bytes of every image that is decoded on the device: image k's decode may still be queued when image k + 1 is staged
+        size_t stageBytes = 0;
+        for (int i = 0; i < sc->TextureCount; i++) if (tex_decoded(sc->Textures[i].format)) stageBytes += (tex_source_bytes(sc->Textures[i]) + 255) & ~(size_t)255;
+        if (stageBytes) HIPC(ctx->texStage.ensure(stageBytes));
+    }
+    size_t stageOff = 0;
     for (int i = 0; i < sc->TextureCount; i++) {
         const idkpt_texture& t = sc->Textures[i];
-        if ((rc = tex_validate(ctx, t, "idkptUploadScene"))) return rc;
         ctx->texData.emplace_back();
-        if ((rc = upload(ctx, ctx->texData.back(), t.rgba, (size_t)t.width * t.height * tex_texel_bytes(t.format)))) return rc;
+        if (tex_decoded(t.format)) {
+            const size_t srcBytes = tex_source_bytes(t);
+            char* staged = (char*)ctx->texStage.p + stageOff; stageOff += (srcBytes + 255) & ~(size_t)255;
+            HIPC(hipMemcpyAsync(staged, t.rgba, srcBytes, hipMemcpyHostToDevice, ctx->stream));
+            HIPC(ctx->texData.back().ensure(std::max<size_t>(tex_resident_bytes(t), 16)));
+            if ((rc = tex_decode_launch(ctx, t, staged, ctx->texData.back().p))) return rc;
+        } else if ((rc = upload(ctx, ctx->texData.back(), t.rgba, tex_resident_bytes(t)))) return rc;
         ctx->texDims.push_back({t.width, t.height}); ctx->texState.push_back(tex_state(t));
     }
     if ((rc = tex_descs_upload(ctx))) return rc;
@@ -538,11 +594,35 @@ static int32_t dev_UpdateTexture(dev_ctx* ctx, int32_t index, const idkpt_textur
     HIPC(hipSetDevice(ctx->device));
     FLUSH();
     HIPC(hipStreamSynchronize(ctx->stream));                                        // (the old image may be released below: nothing in flight reads it any more)
-    { int rc = upload(ctx, ctx->texData[index], t->rgba, (size_t)t->width * t->height * tex_texel_bytes(t->format)); if (rc) return rc; }
+    if (tex_decoded(t->format)) {                                                   // staged, then expanded into the resident format (the synchronisation above and below makes the staging buffer free for the next call)
+        { int rc = upload(ctx, ctx->texStage, t->rgba, tex_source_bytes(*t)); if (rc) return rc; }
+        HIPC(ctx->texData[index].ensure(std::max<size_t>(tex_resident_bytes(*t), 16)));
+        { int rc = tex_decode_launch(ctx, *t, ctx->texStage.p, ctx->texData[index].p); if (rc) return rc; }
+    } else { int rc = upload(ctx, ctx->texData[index], t->rgba, tex_resident_bytes(*t)); if (rc) return rc; }
     HIPC(hipStreamSynchronize(ctx->stream));                                        // (the host's array is borrowed for the call only)
     ctx->texDims[index] = {t->width, t->height}; ctx->texState[index] = tex_state(*t);
     if (!tex_all_finite(*t)) ctx->sceneNoEmission = false;                          // (conservative: the shortcut stays off until the next idkptUploadScene)
     return tex_descs_upload(ctx);
+}
+
+// idkptDownloadTexture: image `index` as the sampler sees it — resident format, size and (dst != NULL) the resident texels
+static int32_t dev_DownloadTexture(dev_ctx* ctx, int32_t index, int32_t* outResidentFormat, int32_t* outWidth, int32_t* outHeight, void* dst, size_t dstBytes)
+{
+    if (!ctx) return IDKPT_ERR_INVALID_ARGUMENT;
+    if (!ctx->haveScene) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptDownloadTexture: no scene uploaded");
+    REQUIRE(index >= 0 && index < ctx->textureCount && (size_t)index < ctx->texData.size(), "idkptDownloadTexture: index out of range");
+    const int32_t fmt = (int32_t)(ctx->texState[index] >> 5), w = ctx->texDims[index].first, h = ctx->texDims[index].second;
+    if (outResidentFormat) *outResidentFormat = fmt;
+    if (outWidth) *outWidth = w;
+    if (outHeight) *outHeight = h;
+    if (!dst) return IDKPT_OK;
+    const size_t bytes = (size_t)w * h * tex_texel_bytes(fmt);
+    REQUIRE(dstBytes >= bytes, "idkptDownloadTexture: destination too small");
+    HIPC(hipSetDevice(ctx->device));
+    FLUSH();
+    HIPC(hipMemcpyAsync(dst, ctx->texData[index].p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    return IDKPT_OK;
 }
 
 static int32_t dev_SetLightCount(dev_ctx* ctx, int32_t count)

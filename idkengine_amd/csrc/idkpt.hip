@@ -31,6 +31,7 @@ using namespace ptd;
 #include "kernels_queue.hpp"
 #include "kernels_frame.hpp"
 #include "kernels_scene.hpp"
+#include "kernels_texture.hpp"
 #include "bvh_gpu.hpp"
 #include "bvh_gpu_full.hpp"
 

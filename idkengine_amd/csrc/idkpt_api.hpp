@@ -639,6 +639,15 @@ int32_t idkptDownloadBuffer(idkpt_ctx* c, int32_t which, size_t offsetBytes, siz
     return rc ? mfail(c, c->dev[0], rc) : IDKPT_OK;
 }
 
+int32_t idkptDownloadTexture(idkpt_ctx* c, int32_t index, int32_t* outResidentFormat, int32_t* outWidth, int32_t* outHeight, void* dst, size_t dstBytes)
+{
+    if (!c) return IDKPT_ERR_INVALID_ARGUMENT;
+    ONE(dev_DownloadTexture(m, index, outResidentFormat, outWidth, outHeight, dst, dstBytes));
+    if (dst) GFLUSH();
+    int rc = dev_DownloadTexture(c->dev[0], index, outResidentFormat, outWidth, outHeight, dst, dstBytes);   // the table is replicated: member 0's copy
+    return rc ? mfail(c, c->dev[0], rc) : IDKPT_OK;
+}
+
 // ray queries are independent: the array is cut into one contiguous piece per device
 int32_t idkptTraceRays(idkpt_ctx* c, const idkpt_ray* rays, size_t count, uint32_t flags, idkpt_hit* hits)
 {

@@ -99,6 +99,21 @@ def make_band_exchange(height, band, group=None):
     return exchange
 
 
+def _texture_meta(t):
+    """What broadcast_scene sends ahead of an image's bytes: array shape and dtype, sampler state, format, width, height."""
+    return (t.data.shape, t.data.dtype.str, t.wrap_s, t.wrap_t, t.mag_filter, t.format, t.width, t.height)
+
+
+def _texture_from_meta(meta, raw):
+    """The gputypes.TextureImage a rank rebuilds from _texture_meta and the bytes that followed it."""
+    from . import gputypes as T
+    shape, dt, ws, wt, mf, fmt, tw, th = meta
+    raw = np.asarray(raw, np.uint8)
+    if fmt in T.TEXFMT_RESIDENT:                                   # a storage format the library decodes on the device: the bytes stay as the host holds them
+        return T.TextureImage.from_storage(fmt, tw, th, raw, ws, wt, mf)
+    return T.TextureImage(np.frombuffer(raw.tobytes(), np.dtype(dt)).reshape(shape).copy(), ws, wt, mf, srgb=(fmt == T.IDKPT_TEXFMT_SRGB8_A8))
+
+
 def broadcast_scene(scene, src=0, device=None, group=None):
     """Replicates a gputypes.Scene from rank `src` to all ranks (returns the scene on every rank).
     On non-source ranks `scene` may be None.  Arrays travel as raw bytes (the structs are the ABI payload)."""
@@ -116,7 +131,7 @@ def broadcast_scene(scene, src=0, device=None, group=None):
         sky = None if scene.sky_faces is None else np.ascontiguousarray(scene.sky_faces, np.float32)
         meta.append((None if sky is None else sky.shape, 0 if sky is None else sky.nbytes))
         imgs = [T.TextureImage.of(t) for t in scene.textures]
-        meta.append((len(imgs), [(t.data.shape, t.data.dtype.str, t.wrap_s, t.wrap_t, t.mag_filter, t.format) for t in imgs], scene.blas_stack_size))
+        meta.append((len(imgs), [_texture_meta(t) for t in imgs], scene.blas_stack_size))
     box = [meta]
     dist.broadcast_object_list(box, src=src, group=group)
     meta = box[0]
@@ -144,10 +159,10 @@ def broadcast_scene(scene, src=0, device=None, group=None):
     ntex, tex_shapes, stack = meta[len(_SCENE_FIELDS) + 1]
     texs = []
     for k in range(ntex):
-        shape, dt, ws, wt, mf, fmt = tex_shapes[k]
+        shape, dt = tex_shapes[k][:2]
         nb = int(np.prod(shape)) * np.dtype(dt).itemsize
         raw = bcast_bytes(T.TextureImage.of(scene.textures[k]).data if rank == src else None, nb)
-        texs.append(T.TextureImage(np.frombuffer(raw.tobytes(), np.dtype(dt)).reshape(shape).copy(), ws, wt, mf, srgb=(fmt == T.IDKPT_TEXFMT_SRGB8_A8)))      # texels AND sampler state travel
+        texs.append(_texture_from_meta(tex_shapes[k], raw))      # texels AND sampler state travel
     if rank != src:
         out.textures = texs
         out.blas_stack_size = stack

@@ -74,7 +74,18 @@ class Texture(C.Structure):
 # enum idkpt_wrap / idkpt_filter / idkpt_texture_format
 IDKPT_WRAP_REPEAT, IDKPT_WRAP_CLAMP_TO_EDGE, IDKPT_WRAP_MIRRORED_REPEAT = range(3)
 IDKPT_FILTER_LINEAR, IDKPT_FILTER_NEAREST = range(2)
-IDKPT_TEXFMT_RGBA32F, IDKPT_TEXFMT_RGBA8, IDKPT_TEXFMT_SRGB8_A8 = range(3)
+(IDKPT_TEXFMT_RGBA32F, IDKPT_TEXFMT_RGBA8, IDKPT_TEXFMT_SRGB8_A8, IDKPT_TEXFMT_R8, IDKPT_TEXFMT_RG8, IDKPT_TEXFMT_R11G11B10F, IDKPT_TEXFMT_BC4_R, IDKPT_TEXFMT_BC5_RG,
+ IDKPT_TEXFMT_BC7_RGBA, IDKPT_TEXFMT_BC7_SRGBA) = range(10)
+# source formats (>= IDKPT_TEXFMT_R8, decoded on the device at upload) -> the resident format the sampler reads
+TEXFMT_RESIDENT = {IDKPT_TEXFMT_R8: IDKPT_TEXFMT_RGBA8, IDKPT_TEXFMT_RG8: IDKPT_TEXFMT_RGBA8, IDKPT_TEXFMT_R11G11B10F: IDKPT_TEXFMT_RGBA32F, IDKPT_TEXFMT_BC4_R: IDKPT_TEXFMT_RGBA32F,
+                   IDKPT_TEXFMT_BC5_RG: IDKPT_TEXFMT_RGBA32F, IDKPT_TEXFMT_BC7_RGBA: IDKPT_TEXFMT_RGBA8, IDKPT_TEXFMT_BC7_SRGBA: IDKPT_TEXFMT_SRGB8_A8}
+
+
+def texture_storage_bytes(format, width, height):
+    """Bytes a host passes for a width x height image of `format` (the table of include/idkpt.h)."""
+    texels, blocks = width * height, ((width + 3) // 4) * ((height + 3) // 4)
+    return {IDKPT_TEXFMT_RGBA32F: texels * 16, IDKPT_TEXFMT_RGBA8: texels * 4, IDKPT_TEXFMT_SRGB8_A8: texels * 4, IDKPT_TEXFMT_R8: texels, IDKPT_TEXFMT_RG8: texels * 2,
+            IDKPT_TEXFMT_R11G11B10F: texels * 4, IDKPT_TEXFMT_BC4_R: blocks * 8, IDKPT_TEXFMT_BC5_RG: blocks * 16, IDKPT_TEXFMT_BC7_RGBA: blocks * 16, IDKPT_TEXFMT_BC7_SRGBA: blocks * 16}[format]
 GL_WRAP = {0x2901: IDKPT_WRAP_REPEAT, 0x812F: IDKPT_WRAP_CLAMP_TO_EDGE, 0x8370: IDKPT_WRAP_MIRRORED_REPEAT}      # GLSampler.WrapMode (glTF sampler.wrapS / wrapT) -> enum idkpt_wrap
 GL_MAG_FILTER = {0x2601: IDKPT_FILTER_LINEAR, 0x2600: IDKPT_FILTER_NEAREST}                                       # GLSampler.MagFilter -> enum idkpt_filter
 
@@ -93,13 +104,37 @@ class TextureImage:
         assert self.data.ndim == 3 and self.data.shape[2] == 4
         self.wrap_s, self.wrap_t, self.mag_filter = int(wrap_s), int(wrap_t), int(mag_filter)
 
+    _size = None    # (width, height) of a from_storage image; otherwise the array's shape says it
+
+    @property
+    def width(self):
+        return self._size[0] if self._size else self.data.shape[1]
+
+    @property
+    def height(self):
+        return self._size[1] if self._size else self.data.shape[0]
+
+    @staticmethod
+    def from_storage(format, width, height, data, wrap_s=IDKPT_WRAP_REPEAT, wrap_t=IDKPT_WRAP_REPEAT, mag_filter=IDKPT_FILTER_LINEAR):
+        """An image in one of the storage formats the library decodes on the device (IDKPT_TEXFMT_R8 .. IDKPT_TEXFMT_BC7_SRGBA): `data` is the bytes as the engine holds them —
+        any array or buffer of exactly texture_storage_bytes(format, width, height) bytes (tightly packed rows, or 4x4 blocks row-major over the block grid)."""
+        format, width, height = int(format), int(width), int(height)
+        assert format in TEXFMT_RESIDENT, "from_storage is for the formats decoded on the device; RGBA32F / RGBA8 / SRGB8_A8 images are made by the constructor"
+        assert width > 0 and height > 0
+        t = TextureImage.__new__(TextureImage)
+        t.data = np.ascontiguousarray(np.frombuffer(np.ascontiguousarray(data).tobytes(), np.uint8))
+        assert t.data.nbytes == texture_storage_bytes(format, width, height), (t.data.nbytes, texture_storage_bytes(format, width, height))
+        t.format, t._size = format, (width, height)
+        t.wrap_s, t.wrap_t, t.mag_filter = int(wrap_s), int(wrap_t), int(mag_filter)
+        return t
+
     @staticmethod
     def of(t):
         return t if isinstance(t, TextureImage) else TextureImage(t)
 
     def fill(self, rec):
         """Writes this image into a Texture record; the record borrows self.data."""
-        rec.height, rec.width, rec.rgba = self.data.shape[0], self.data.shape[1], self.data.ctypes.data
+        rec.height, rec.width, rec.rgba = self.height, self.width, self.data.ctypes.data
         rec.wrapS, rec.wrapT, rec.magFilter, rec.format = self.wrap_s, self.wrap_t, self.mag_filter, self.format
 
 

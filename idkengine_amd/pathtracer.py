@@ -371,6 +371,14 @@ class PathTracer:
         t = T.TextureImage.of(image); rec = T.Texture(); t.fill(rec)
         self._check(self._L.idkptUpdateTexture(self._ctx, int(index), C.byref(rec)))
 
+    def DownloadTexture(self, index):
+        """idkptDownloadTexture: image `index` as the sampler sees it — (resident format, (h, w, 4) float32 array for RGBA32F, uint8 array for RGBA8 / SRGB8_A8)."""
+        fmt, w, h = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(self._L.idkptDownloadTexture(self._ctx, int(index), C.byref(fmt), C.byref(w), C.byref(h), None, 0))
+        out = np.zeros((h.value, w.value, 4), np.float32 if fmt.value == T.IDKPT_TEXFMT_RGBA32F else np.uint8)
+        self._check(self._L.idkptDownloadTexture(self._ctx, int(index), C.byref(fmt), C.byref(w), C.byref(h), out.ctypes.data, out.nbytes))
+        return fmt.value, out
+
     def enable_counters(self, on=True):
         self._check(self._L.idkptEnableCounters(self._ctx, 1 if on else 0))
 

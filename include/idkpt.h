@@ -62,14 +62,45 @@ enum idkpt_buffer {
  * The zero value of every state field is the round-5 behaviour (REPEAT, REPEAT, LINEAR, RGBA32F): a zero-initialised struct with width / height / rgba set samples as before. */
 enum idkpt_wrap { IDKPT_WRAP_REPEAT = 0 /* GL_REPEAT 0x2901 */, IDKPT_WRAP_CLAMP_TO_EDGE = 1 /* GL_CLAMP_TO_EDGE 0x812F */, IDKPT_WRAP_MIRRORED_REPEAT = 2 /* GL_MIRRORED_REPEAT 0x8370 */ };
 enum idkpt_filter { IDKPT_FILTER_LINEAR = 0 /* GL_LINEAR 0x2601 */, IDKPT_FILTER_NEAREST = 1 /* GL_NEAREST 0x2600 */ };
-enum idkpt_texture_format { IDKPT_TEXFMT_RGBA32F = 0 /* 16 B / texel */, IDKPT_TEXFMT_RGBA8 = 1 /* GL_RGBA8: 4 B / texel, UNORM */, IDKPT_TEXFMT_SRGB8_A8 = 2 /* GL_SRGB8_ALPHA8: 4 B / texel */ };
+/* Values 0-2 are the RESIDENT formats: what the sampler reads, uploaded as they are.  Values 3-9 (ABI 4) are SOURCE formats, the ones the engine really holds
+ * (Utils/ModelLoader.cs:938-973): the host passes the bytes as it keeps them, the library copies them to the device and one kernel decodes them ONCE, at idkptUploadScene /
+ * idkptUpdateTexture, into a resident format (csrc/kernels_texture.hpp); sampling is unchanged and nothing stays compressed on the device.  Only mip level 0 takes part (the
+ * path tracer samples at level of detail 0, see above).  Missing channels read as GL reads them: 0, 0, 1.
+ *
+ *   value  name                      bytes the host passes                                        resident   resident texel
+ *   3      IDKPT_TEXFMT_R8           w*h x 1                                                      RGBA8      (r, 0, 0, 255)
+ *   4      IDKPT_TEXFMT_RG8          w*h x 2                                                      RGBA8      (r, g, 0, 255)
+ *   5      IDKPT_TEXFMT_R11G11B10F   w*h x 4 (GL packing: R bits 0-10, G 11-21, B 22-31)          RGBA32F    (r, g, b, 1.0)
+ *   6      IDKPT_TEXFMT_BC4_R        ceil(w/4)*ceil(h/4) x 8  (RGTC1 unsigned)                    RGBA32F    (r, 0, 0, 1)
+ *   7      IDKPT_TEXFMT_BC5_RG       ceil(w/4)*ceil(h/4) x 16 (RGTC2 unsigned: R block, G block)  RGBA32F    (r, g, 0, 1)
+ *   8      IDKPT_TEXFMT_BC7_RGBA     ceil(w/4)*ceil(h/4) x 16 (BPTC UNORM)                        RGBA8      decoded bytes
+ *   9      IDKPT_TEXFMT_BC7_SRGBA    the same                                                     SRGB8_A8   decoded bytes
+ *
+ * Linear data is tightly packed, row 0 = v 0.  Blocks are row-major over the block grid, block row 0 covers texel rows 0-3; texels of edge blocks beyond width / height are
+ * discarded.  The decode definitions (the contract; tests/test_gpu_texfmt.py holds the device to them bit for bit):
+ *  - R11G11B10F: unsigned fields, 5-bit exponent e (bias 15) above a 6-bit (R, G) or 5-bit (B) mantissa m of M bits.  e = 0: m / 2^M * 2^-14; e = 31: +Inf (m = 0) or the NaN
+ *    0x7fc00000 (m != 0); otherwise (1 + m / 2^M) * 2^(e - 15).  Every finite value is exact in float32.
+ *  - BC4 / each half of BC5: bytes r0, r1, then 48 bits of 3-bit codes; texel i = x + 4y has bits [3i, 3i + 2] of that 48-bit little-endian integer.  r0 > r1: code 0 -> r0,
+ *    1 -> r1, k = 2..7 -> ((8 - k) r0 + (k - 1) r1) / 7; otherwise k = 2..5 -> ((6 - k) r0 + (k - 1) r1) / 5, 6 -> 0, 7 -> 1.  The resident float is that real value / 255
+ *    rounded ONCE: the integer numerator divided in float32 by 1785.0f (7 * 255) or 1275.0f (5 * 255), with r0, r1 and the constants through the same expression (7 r0 / 1785,
+ *    1275 / 1275: 255 -> exactly 1.0f).  Hence the float resident form: GPUs decode RGTC above 8 bits, and a byte would be a second, invented rounding.  Cost: 16 B per texel.
+ *  - BC7: ARB_texture_compression_bptc / Khronos Data Format 1.3, BPTC, which define the result to the bit.  Mode = index of the lowest set bit of byte 0 (byte 0 == 0 is
+ *    reserved and decodes to (0, 0, 0, 0)).  Per mode (subsets, partition bits, rotation bits, index-selection bit, colour bits, alpha bits, p-bits, index bits, second index
+ *    bits): 0 (3,4,0,0,4,0,per endpoint,3,-)  1 (2,6,0,0,6,0,shared per subset,3,-)  2 (3,6,0,0,5,0,none,2,-)  3 (2,6,0,0,7,0,per endpoint,2,-)  4 (1,0,2,1,5,6,none,2,3)
+ *    5 (1,0,2,0,7,8,none,2,2)  6 (1,0,0,0,7,7,per endpoint,4,-)  7 (2,6,0,0,5,5,per endpoint,2,-).  Field order: all R endpoints, all G, all B, all A, p-bits, indices (each
+ *    subset's anchor index one bit shorter; modes 4 / 5: the 2-bit set first).  Endpoints widen to 8 bits by left shift + replication of their high bits; a texel is
+ *    ((64 - w) e0 + w e1 + 32) >> 6 with w from {0,21,43,64} / {0,9,18,27,37,46,55,64} / {0,4,9,13,17,21,26,30,34,38,43,47,51,55,60,64}; rotation swaps A with R / G / B after
+ *    interpolation; modes without alpha give 255.  Partition and anchor tables: csrc/kernels_texture.hpp; fixture of every (mode, selector): tests/golden/texfmt. */
+enum idkpt_texture_format { IDKPT_TEXFMT_RGBA32F = 0 /* 16 B / texel */, IDKPT_TEXFMT_RGBA8 = 1 /* GL_RGBA8: 4 B / texel, UNORM */, IDKPT_TEXFMT_SRGB8_A8 = 2 /* GL_SRGB8_ALPHA8: 4 B / texel */,
+                            IDKPT_TEXFMT_R8 = 3 /* GL_R8 */, IDKPT_TEXFMT_RG8 = 4 /* GL_RG8 */, IDKPT_TEXFMT_R11G11B10F = 5 /* GL_R11F_G11F_B10F */, IDKPT_TEXFMT_BC4_R = 6 /* GL_COMPRESSED_RED_RGTC1 */,
+                            IDKPT_TEXFMT_BC5_RG = 7 /* GL_COMPRESSED_RG_RGTC2 */, IDKPT_TEXFMT_BC7_RGBA = 8 /* GL_COMPRESSED_RGBA_BPTC_UNORM */, IDKPT_TEXFMT_BC7_SRGBA = 9 /* GL_COMPRESSED_SRGB_ALPHA_BPTC_UNORM */ };
 typedef struct idkpt_texture {
     int32_t width, height;
-    const void* rgba;  /* width*height texels, row-major, row 0 = v 0: 4 floats each (RGBA32F) or 4 bytes each (RGBA8, SRGB8_A8) */
+    const void* rgba;  /* width*height texels, row-major, row 0 = v 0: 4 floats each (RGBA32F) or 4 bytes each (RGBA8, SRGB8_A8); formats 3-9: the bytes of the table above */
     int32_t wrapS, wrapT;   /* enum idkpt_wrap: GLSampler.SamplerState.WrapModeS / WrapModeT */
     int32_t magFilter;      /* enum idkpt_filter: GLSampler.SamplerState.MagFilter */
     int32_t format;         /* enum idkpt_texture_format */
-} idkpt_texture;            /* 32 B (ABI 3; round 5: 16 B) */
+} idkpt_texture;            /* 32 B (ABI 3; round 5: 16 B); formats 3-9: ABI 4 */
 
 /* ---- adjacent consumers of the traversal core ---- */
 /* One ray of a batched query = one call of TraceRay(ray, hitInfo, traceLights, maxDist)
@@ -165,10 +196,10 @@ typedef struct idkpt_stats {
     uint32_t InstUnifiedTopDepth;  /* depth of that top */
 } idkpt_stats;
 /* The layout above only ever GROWS at its end, and IDKPT_ABI_VERSION counts the growths (and every other change a host compiled against an older header could trip over: new
- * enum values of idkpt_buffer, new fields of idkpt_texture).  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
+ * enum values of idkpt_buffer or idkpt_texture_format, new fields of idkpt_texture).  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
  * of ITS struct to idkptGetStatsSized and gets exactly that many bytes; idkptGetStats(ctx, out) is idkptGetStatsSized(ctx, out, sizeof(idkpt_stats)) of the header the LIBRARY
  * was built with — for hosts built from the same tree.  idkptGetAbiVersion() lets a host refuse a library older than the header it was written against. */
-#define IDKPT_ABI_VERSION 3
+#define IDKPT_ABI_VERSION 4
 
 /* ---- lifetime --------------------------------------------------------------------------- */
 /* new PathTracer(w,h,settings) (PathTracer.cs:170-212).  deviceCount = 1: the reference's situation, one GPU.
@@ -288,6 +319,10 @@ IDKPT_API int32_t idkptUpdateBuffer(idkpt_ctx* ctx, int32_t which, size_t offset
 /* Replaces image `index` of the texture table (contents, size, format and sampler state): a streamed-in higher mip as base level, a changed sampler.  Stream-ordered behind the
  * samples already queued (they are launched first); the accumulation is the host's to reset, as after any scene update. */
 IDKPT_API int32_t idkptUpdateTexture(idkpt_ctx* ctx, int32_t index, const idkpt_texture* texture);
+/* Image `index` of the texture table as the sampler sees it: its resident format (enum idkpt_texture_format 0-2), its size and — dst != NULL — its width * height * (16 | 4)
+ * resident bytes (queued samples are launched first and the call synchronises, like the other Download calls; dst == NULL only fills the three outputs, any of which may be
+ * NULL).  INVALID_ARGUMENT: index out of range, dstBytes too small; INVALID_OPERATION: no scene.  A multi-device context reads its first member's copy. */
+IDKPT_API int32_t idkptDownloadTexture(idkpt_ctx* ctx, int32_t index, int32_t* outResidentFormat, int32_t* outWidth, int32_t* outHeight, void* dst, size_t dstBytes);
 IDKPT_API int32_t idkptSetLightCount(idkpt_ctx* ctx, int32_t count);
 /* BVH.TlasBuild upload (Bvh/BVH.cs:278-298): host-built TLAS nodes replace SSBO 27 */
 IDKPT_API int32_t idkptBuildTlas(idkpt_ctx* ctx, const GpuTlasNode* nodes, int32_t nodeCount);
