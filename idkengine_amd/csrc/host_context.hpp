@@ -148,6 +148,8 @@ struct dev_ctx {
     uint8_t lastSlots[VB_COUNT] = {0}; bool lastMulti = false;   // ... the one set of slots of a single-version batch, or "per sample: verTab"
     DevBuf verTab; uint32_t* hVerTab = nullptr; hipEvent_t evVer[2] = {nullptr, nullptr}; int verHalf = 0;   // per-sample version table of the batch being launched (pinned, double-buffered staging)
     char* hStage = nullptr; hipEvent_t evStage[4] = {nullptr, nullptr, nullptr, nullptr}; int stageNext = 0;   // pinned ring for small host -> device updates (joint matrices, transforms): no stream synchronisation per call
+    char* hSkyStage = nullptr; size_t hSkyStageBytes = 0; hipEvent_t evSkyStage = nullptr;   // pinned staging of the host faces idkptUpdateSky uploads (its copy is asynchronous: the call does not wait for the stream); the event = the last copy that read it
+    hipEvent_t evSky = nullptr;                       // multi-device contexts: this member's last write to / last peer read of its sky (idkpt_api.hpp idkptUpdateSky)
     int (*groupFlushAll)(void* user) = nullptr;      // member of a multi-device context: launches what ALL members have queued (a member never flushes on its own)
     // wavefront state
     DevBuf pmList;                                       // the first bounce's work list in pixel-major order (k_shade_first)

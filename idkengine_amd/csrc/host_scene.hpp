@@ -141,6 +141,9 @@ static int32_t dev_Destroy(dev_ctx* ctx)
     if (ctx->hVerTab) (void)hipHostFree(ctx->hVerTab);
     for (int i = 0; i < 2; i++) if (ctx->evVer[i]) (void)hipEventDestroy(ctx->evVer[i]);
     if (ctx->hStage) (void)hipHostFree(ctx->hStage);
+    if (ctx->hSkyStage) (void)hipHostFree(ctx->hSkyStage);
+    if (ctx->evSkyStage) (void)hipEventDestroy(ctx->evSkyStage);
+    if (ctx->evSky) (void)hipEventDestroy(ctx->evSky);
     for (int i = 0; i < 4; i++) if (ctx->evStage[i]) (void)hipEventDestroy(ctx->evStage[i]);
     if (ctx->evFrame[0]) (void)hipEventDestroy(ctx->evFrame[0]);
     if (ctx->evFrame[1]) (void)hipEventDestroy(ctx->evFrame[1]);
@@ -621,6 +624,127 @@ static int32_t dev_DownloadTexture(dev_ctx* ctx, int32_t index, int32_t* outResi
     HIPC(hipSetDevice(ctx->device));
     FLUSH();
     HIPC(hipMemcpyAsync(dst, ctx->texData[index].p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    return IDKPT_OK;
+}
+
+// ---- the sky (idkptComputeSky / idkptUpdateSky / idkptDownloadSky; kernels_sky.hpp) -----------------------------------------------------------------------------------
+// The resident form is idkptUploadScene's: 6 S^2 float4 in ctx->sky, skySize = S.  The sky is not versioned (kernels_shade.hpp k_shade_last, host_schedule.hpp), so what every
+// scene update does comes first: the queued samples are launched and a deferred last bounce completed (FLUSH), and the rays the fast path left unmaterialised — tile classes
+// 1-6 and 8 and the deferred bounce leave radiance that is only produced on demand, from the sky — are completed while the OLD sky is resident.  The new sky is then enqueued
+// on the context's stream, behind all of that; nothing waits for the stream, except once when S outgrows the allocation (the old one is released: as dev_BuildTlas does).
+// The tile classes depend on skySize (kernels_trace.hpp k_classify_tiles: 7 no sky, 8 textured, 1-6 constant faces); they are derived anew for every batch from the DScene
+// of that batch, and the one consumer that outlives a batch (k_regen_culled: contFlag + lastFrame) has just run — no classification survives this call.
+static int sky_begin(dev_ctx* ctx, int32_t S)
+{
+    HIPC(hipSetDevice(ctx->device));
+    FLUSH();
+    { int rc = materialize_culled_rays(ctx); if (rc) return rc; }   // while the old sky is still resident
+    const size_t bytes = std::max<size_t>((size_t)6 * S * S * 16, 16);
+    if (!ctx->sky.p || bytes > ctx->sky.bytes) {
+        HIPC(hipStreamSynchronize(ctx->stream));                    // (kernels in flight read the allocation that is released here)
+        ctx->skySize = 0;
+        HIPC(ctx->sky.ensure(bytes));
+    }
+    return IDKPT_OK;
+}
+
+static int32_t dev_ComputeSky(dev_ctx* ctx, int32_t faceSize, const idkpt_atmosphere* a)
+{
+    if (!ctx || !a) return IDKPT_ERR_INVALID_ARGUMENT;
+    if (!ctx->haveScene) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptComputeSky: no scene uploaded");
+    REQUIRE(faceSize >= 1 && faceSize <= 4096, "idkptComputeSky: faceSize must be in 1..4096");
+    REQUIRE(a->ISteps >= 1 && a->ISteps <= 4096 && a->JSteps >= 1 && a->JSteps <= 4096, "idkptComputeSky: ISteps and JSteps must be in 1..4096");
+    auto fin = [](float v) { return v - v == 0.0f; };
+    REQUIRE(fin(a->LightIntensity) && fin(a->Azimuth) && fin(a->Elevation), "idkptComputeSky: LightIntensity, Azimuth and Elevation must be finite");
+    { int rc = sky_begin(ctx, faceSize); if (rc) return rc; }
+    skyk::AtmoParams p = {a->ISteps, a->JSteps, a->LightIntensity > 0.0f ? a->LightIntensity : 0.0f /* AtmosphericScatterer.Compute: MaxNative(LightIntensity, 0) */, a->Azimuth, a->Elevation};
+    const uint32_t texels = 6u * (uint32_t)faceSize * (uint32_t)faceSize;
+    hipLaunchKernelGGL(k_sky_atmosphere, dim3((texels + 255u) / 256u), dim3(256), 0, ctx->stream, ctx->sky.as<float4>(), (int)faceSize, p);
+    HIPC(hipGetLastError());
+    ctx->skySize = faceSize;
+    return IDKPT_OK;
+}
+
+static int32_t sky_validate_update(dev_ctx* ctx, int32_t faceSize, int32_t format, const void* faces)
+{
+    if (!ctx->haveScene) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptUpdateSky: no scene uploaded");
+    REQUIRE(faceSize >= 0 && faceSize <= 4096, "idkptUpdateSky: faceSize must be in 0..4096 (0: no sky)");
+    REQUIRE(format == IDKPT_TEXFMT_RGBA32F || format == IDKPT_TEXFMT_RGBA8 || format == IDKPT_TEXFMT_SRGB8_A8, "idkptUpdateSky: format must be IDKPT_TEXFMT_RGBA32F, RGBA8 or SRGB8_A8");
+    return IDKPT_OK;
+}
+
+static int32_t dev_UpdateSky(dev_ctx* ctx, int32_t faceSize, int32_t format, const void* faces)
+{
+    if (!ctx) return IDKPT_ERR_INVALID_ARGUMENT;
+    { int rc = sky_validate_update(ctx, faceSize, format, faces); if (rc) return rc; }
+    const int32_t S = (faces && faceSize > 0) ? faceSize : 0;
+    { int rc = sky_begin(ctx, S); if (rc) return rc; }
+    if (S == 0) { ctx->skySize = 0; return IDKPT_OK; }               // no sky: black (SampleSky)
+    const size_t texels = (size_t)6 * S * S, srcBytes = texels * (format == IDKPT_TEXFMT_RGBA32F ? 16 : 4);
+    // The host's array is borrowed for the call only and the copy must not make the call wait for the stream: the bytes go through a pinned buffer of the context's own
+    // (the pattern of staged_upload, one buffer of the size of the largest sky so far; only the PREVIOUS sky upload's copy is waited for, normally long finished).
+    if (!ctx->evSkyStage) HIPC(hipEventCreateWithFlags(&ctx->evSkyStage, hipEventDisableTiming));
+    else HIPC(hipEventSynchronize(ctx->evSkyStage));
+    if (ctx->hSkyStageBytes < srcBytes) {
+        if (ctx->hSkyStage) (void)hipHostFree(ctx->hSkyStage);
+        ctx->hSkyStage = nullptr; ctx->hSkyStageBytes = 0;
+        HIPC(hipHostMalloc((void**)&ctx->hSkyStage, srcBytes, hipHostMallocDefault));
+        ctx->hSkyStageBytes = srcBytes;
+    }
+    memcpy(ctx->hSkyStage, faces, srcBytes);
+    if (format == IDKPT_TEXFMT_RGBA32F) {
+        HIPC(hipMemcpyAsync(ctx->sky.p, ctx->hSkyStage, srcBytes, hipMemcpyHostToDevice, ctx->stream));
+    } else {
+        // 8-bit faces are staged on the device and expanded by one kernel, as the texture table's source formats are (texStage: free here — idkptUploadScene and idkptUpdateTexture
+        // end with the stream idle, and an earlier expansion of this function is ordered before this copy on the stream; it is reallocated only after a synchronisation)
+        { int rc = tex_srgb_lut(ctx); if (rc) return rc; }
+        if (ctx->texStage.bytes < srcBytes) { HIPC(hipStreamSynchronize(ctx->stream)); HIPC(ctx->texStage.ensure(srcBytes)); }
+        HIPC(hipMemcpyAsync(ctx->texStage.p, ctx->hSkyStage, srcBytes, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(k_sky_expand, dim3((unsigned)((texels + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)ctx->texStage.p, ctx->sky.as<float4>(), (uint32_t)texels, (int)format, (const float*)ctx->srgbLut.as<float>());
+        HIPC(hipGetLastError());
+    }
+    HIPC(hipEventRecord(ctx->evSkyStage, ctx->stream));
+    ctx->skySize = S;
+    return IDKPT_OK;
+}
+
+// multi-device contexts (idkpt_api.hpp idkptUpdateSky): this member adopts the sky member `src` uploaded.  copy: device to device like the scene buffers (member_copy), ordered
+// behind src->evSky — recorded on the source's stream after its upload (sky_mark) — and marked in turn, so that the source can wait for this read before it writes its sky
+// again; !copy: only the room is made (the caller moves the bytes: one RCCL broadcast over all members' streams, which orders itself).
+static int sky_mark(dev_ctx* ctx)
+{
+    HIPC(hipSetDevice(ctx->device));
+    if (!ctx->evSky) HIPC(hipEventCreateWithFlags(&ctx->evSky, hipEventDisableTiming));
+    HIPC(hipEventRecord(ctx->evSky, ctx->stream));
+    return IDKPT_OK;
+}
+static int32_t dev_SkyFrom(dev_ctx* ctx, dev_ctx* src, bool copy)
+{
+    if (!ctx || !src) return IDKPT_ERR_INVALID_ARGUMENT;
+    { int rc = sky_begin(ctx, src->skySize); if (rc) return rc; }
+    if (src->skySize > 0 && copy) {
+        HIPC(hipStreamWaitEvent(ctx->stream, src->evSky, 0));
+        HIPC(member_copy(ctx->peer, ctx->sky.p, ctx->device, src->sky.p, src->device, (size_t)6 * src->skySize * src->skySize * 16, ctx->stream));
+        { int rc = sky_mark(ctx); if (rc) return rc; }
+    }
+    ctx->skySize = src->skySize;
+    return IDKPT_OK;
+}
+
+// idkptDownloadSky: the resident faces (always RGBA32F)
+static int32_t dev_DownloadSky(dev_ctx* ctx, int32_t* outFaceSize, float* dst, size_t dstBytes)
+{
+    if (!ctx) return IDKPT_ERR_INVALID_ARGUMENT;
+    if (!ctx->haveScene) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptDownloadSky: no scene uploaded");
+    if (outFaceSize) *outFaceSize = ctx->skySize;
+    if (!dst) return IDKPT_OK;
+    const size_t bytes = (size_t)6 * ctx->skySize * ctx->skySize * 16;
+    REQUIRE(dstBytes >= bytes, "idkptDownloadSky: destination too small");
+    if (bytes == 0) return IDKPT_OK;
+    HIPC(hipSetDevice(ctx->device));
+    FLUSH();
+    HIPC(hipMemcpyAsync(dst, ctx->sky.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIPC(hipStreamSynchronize(ctx->stream));
     return IDKPT_OK;
 }

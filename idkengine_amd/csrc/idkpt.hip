@@ -32,6 +32,7 @@ using namespace ptd;
 #include "kernels_frame.hpp"
 #include "kernels_scene.hpp"
 #include "kernels_texture.hpp"
+#include "kernels_sky.hpp"
 #include "bvh_gpu.hpp"
 #include "bvh_gpu_full.hpp"
 

@@ -648,6 +648,59 @@ int32_t idkptDownloadTexture(idkpt_ctx* c, int32_t index, int32_t* outResidentFo
     return rc ? mfail(c, c->dev[0], rc) : IDKPT_OK;
 }
 
+// ---- the sky: every member holds its own copy (like every scene buffer)
+// member 0's stream waits for the peers' device-to-device reads of its sky (a previous idkptUpdateSky) before anything overwrites it
+static int group_sky_writable(idkpt_ctx* c)
+{
+    dev_ctx* m0 = c->dev[0];
+    GHIP(hipSetDevice(m0->device));
+    for (size_t d = 1; d < c->n(); d++) if (c->dev[d]->evSky) GHIP(hipStreamWaitEvent(m0->stream, c->dev[d]->evSky, 0));
+    return IDKPT_OK;
+}
+// every member runs the kernel itself: deterministic, and far cheaper than moving the faces between devices
+int32_t idkptComputeSky(idkpt_ctx* c, int32_t faceSize, const idkpt_atmosphere* atmosphere)
+{
+    if (!c) return IDKPT_ERR_INVALID_ARGUMENT;
+    ONE(dev_ComputeSky(m, faceSize, atmosphere));
+    if (!atmosphere) return IDKPT_ERR_INVALID_ARGUMENT;
+    GFLUSH();
+    { int rc = group_sky_writable(c); if (rc) return rc; }
+    ALL(dev_ComputeSky(m, faceSize, atmosphere));       // (validates; nothing is changed when it fails on the first member)
+    return IDKPT_OK;
+}
+// the faces cross PCIe once, to member 0 (expanded there when they are 8-bit), and reach the other members the way the scene does: one RCCL broadcast, or peer copies
+int32_t idkptUpdateSky(idkpt_ctx* c, int32_t faceSize, int32_t format, const void* faces)
+{
+    if (!c) return IDKPT_ERR_INVALID_ARGUMENT;
+    ONE(dev_UpdateSky(m, faceSize, format, faces));
+    dev_ctx* m0 = c->dev[0];
+    { int rc = sky_validate_update(m0, faceSize, format, faces); if (rc) return mfail(c, m0, rc); }
+    GFLUSH();
+    { int rc = group_sky_writable(c); if (rc) return rc; }
+    { int rc = dev_UpdateSky(m0, faceSize, format, faces); if (rc) return mfail(c, m0, rc); }
+    { int rc = sky_mark(m0); if (rc) return mfail(c, m0, rc); }
+    const size_t n = c->n(), bytes = (size_t)6 * m0->skySize * m0->skySize * 16;
+    bool moved = false;
+    if (bytes && group_rccl(c)) {
+        for (size_t d = 1; d < n; d++) { int rc = dev_SkyFrom(c->dev[d], m0, false); if (rc) return mfail(c, c->dev[d], rc); }
+        std::vector<int> devs; std::vector<hipStream_t> streams; std::vector<void*> dst;
+        for (dev_ctx* m : c->dev) { devs.push_back(m->device); streams.push_back(m->stream); dst.push_back(m->sky.p); }
+        moved = c->rccl.broadcast(dst, bytes, devs, streams);
+        if (!moved) group_rccl_failed(c);               // (the same buffers are filled again by peer copies)
+    }
+    if (!moved) for (size_t d = 1; d < n; d++) { int rc = dev_SkyFrom(c->dev[d], m0, true); if (rc) return mfail(c, c->dev[d], rc); }
+    (void)hipSetDevice(m0->device);
+    return IDKPT_OK;
+}
+int32_t idkptDownloadSky(idkpt_ctx* c, int32_t* outFaceSize, float* dst, size_t dstBytes)
+{
+    if (!c) return IDKPT_ERR_INVALID_ARGUMENT;
+    ONE(dev_DownloadSky(m, outFaceSize, dst, dstBytes));
+    if (dst) GFLUSH();
+    int rc = dev_DownloadSky(c->dev[0], outFaceSize, dst, dstBytes);   // every member holds the same faces: member 0's copy
+    return rc ? mfail(c, c->dev[0], rc) : IDKPT_OK;
+}
+
 // ray queries are independent: the array is cut into one contiguous piece per device
 int32_t idkptTraceRays(idkpt_ctx* c, const idkpt_ray* rays, size_t count, uint32_t flags, idkpt_hit* hits)
 {

@@ -159,6 +159,14 @@ class SceneDesc(C.Structure):
     ]
 
 
+class Atmosphere(C.Structure):
+    """idkpt_atmosphere = AtmosphericScatterer.GpuSettings (Source/Render/AtmosphericScatterer.cs:9-20), same order; the defaults are the reference's."""
+    _fields_ = [("ISteps", C.c_int32), ("JSteps", C.c_int32), ("LightIntensity", C.c_float), ("Azimuth", C.c_float), ("Elevation", C.c_float)]
+
+    def __init__(self, ISteps=40, JSteps=8, LightIntensity=15.0, Azimuth=0.0, Elevation=0.0):
+        super().__init__(int(ISteps), int(JSteps), float(LightIntensity), float(Azimuth), float(Elevation))
+
+
 class Stats(C.Structure):
     _fields_ = [("RaysTraced", C.c_uint64), ("PrimaryRays", C.c_uint64), ("Frames", C.c_uint64),
                 ("LastAliveCounts", C.c_uint32 * 16), ("LastTraceMs", C.c_float), ("LastFrameMs", C.c_float),

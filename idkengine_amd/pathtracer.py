@@ -379,6 +379,42 @@ class PathTracer:
         self._check(self._L.idkptDownloadTexture(self._ctx, int(index), C.byref(fmt), C.byref(w), C.byref(h), out.ctypes.data, out.nbytes))
         return fmt.value, out
 
+    # ---- the sky without a scene upload (idkptComputeSky / idkptUpdateSky / idkptDownloadSky)
+    def ComputeSky(self, size=128, atmosphere=None):
+        """AtmosphericScatterer.Compute on the device: the six size x size faces of the procedural sky (gputypes.Atmosphere; default: the reference's 40, 8, 15, 0, 0)
+        become the scene's sky.  Stream-ordered; the accumulation is the caller's to reset."""
+        a = atmosphere if atmosphere is not None else T.Atmosphere()
+        if not isinstance(a, T.Atmosphere):
+            raise TypeError("ComputeSky: atmosphere must be a gputypes.Atmosphere")
+        self._check(self._L.idkptComputeSky(self._ctx, int(size), C.addressof(a)))
+
+    def UpdateSky(self, faces, format=T.IDKPT_TEXFMT_RGBA32F):
+        """idkptUpdateSky: `faces` is None (no sky: black) or a C-contiguous (6, S, S, 4) array — float32 for IDKPT_TEXFMT_RGBA32F, uint8 for IDKPT_TEXFMT_RGBA8 /
+        IDKPT_TEXFMT_SRGB8_A8 (face order +X, -X, +Y, -Y, +Z, -Z).  The array is checked against `format` here: the library only sees a pointer."""
+        format = int(format)
+        if format not in (T.IDKPT_TEXFMT_RGBA32F, T.IDKPT_TEXFMT_RGBA8, T.IDKPT_TEXFMT_SRGB8_A8):
+            raise ValueError(f"UpdateSky: format {format} is not IDKPT_TEXFMT_RGBA32F, RGBA8 or SRGB8_A8")
+        if faces is None:
+            self._check(self._L.idkptUpdateSky(self._ctx, 0, format, None))
+            return
+        want = np.float32 if format == T.IDKPT_TEXFMT_RGBA32F else np.uint8
+        if not isinstance(faces, np.ndarray) or faces.dtype != want:
+            raise TypeError(f"UpdateSky: format {format} takes a {np.dtype(want).name} array, got {getattr(faces, 'dtype', type(faces).__name__)}")
+        if faces.ndim != 4 or faces.shape[0] != 6 or faces.shape[3] != 4 or faces.shape[1] != faces.shape[2] or faces.shape[1] < 1:
+            raise ValueError(f"UpdateSky: faces must have shape (6, S, S, 4), got {faces.shape}")
+        if not faces.flags["C_CONTIGUOUS"]:
+            raise ValueError("UpdateSky: faces must be C-contiguous (np.ascontiguousarray)")
+        self._check(self._L.idkptUpdateSky(self._ctx, int(faces.shape[1]), format, faces.ctypes.data))
+
+    def DownloadSky(self):
+        """idkptDownloadSky: the resident faces, a (6, S, S, 4) float32 array (S = 0: no sky)."""
+        s = C.c_int32()
+        self._check(self._L.idkptDownloadSky(self._ctx, C.byref(s), None, 0))
+        out = np.zeros((6, s.value, s.value, 4), np.float32)
+        if s.value:
+            self._check(self._L.idkptDownloadSky(self._ctx, C.byref(s), out.ctypes.data, out.nbytes))
+        return out
+
     def enable_counters(self, on=True):
         self._check(self._L.idkptEnableCounters(self._ctx, 1 if on else 0))
 

@@ -196,10 +196,10 @@ typedef struct idkpt_stats {
     uint32_t InstUnifiedTopDepth;  /* depth of that top */
 } idkpt_stats;
 /* The layout above only ever GROWS at its end, and IDKPT_ABI_VERSION counts the growths (and every other change a host compiled against an older header could trip over: new
- * enum values of idkpt_buffer or idkpt_texture_format, new fields of idkpt_texture).  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
+ * enum values of idkpt_buffer or idkpt_texture_format, new fields of idkpt_texture, new entry points: 5 = idkptComputeSky / idkptUpdateSky / idkptDownloadSky).  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
  * of ITS struct to idkptGetStatsSized and gets exactly that many bytes; idkptGetStats(ctx, out) is idkptGetStatsSized(ctx, out, sizeof(idkpt_stats)) of the header the LIBRARY
  * was built with — for hosts built from the same tree.  idkptGetAbiVersion() lets a host refuse a library older than the header it was written against. */
-#define IDKPT_ABI_VERSION 4
+#define IDKPT_ABI_VERSION 5
 
 /* ---- lifetime --------------------------------------------------------------------------- */
 /* new PathTracer(w,h,settings) (PathTracer.cs:170-212).  deviceCount = 1: the reference's situation, one GPU.
@@ -323,6 +323,24 @@ IDKPT_API int32_t idkptUpdateTexture(idkpt_ctx* ctx, int32_t index, const idkpt_
  * resident bytes (queued samples are launched first and the call synchronises, like the other Download calls; dst == NULL only fills the three outputs, any of which may be
  * NULL).  INVALID_ARGUMENT: index out of range, dstBytes too small; INVALID_OPERATION: no scene.  A multi-device context reads its first member's copy. */
 IDKPT_API int32_t idkptDownloadTexture(idkpt_ctx* ctx, int32_t index, int32_t* outResidentFormat, int32_t* outWidth, int32_t* outHeight, void* dst, size_t dstBytes);
+/* ---- the sky without a scene upload (ABI 5; SkyBoxManager, Source/Render/SkyBoxManager.cs) ----
+ * idkpt_scene_desc.SkyFaces stays; these three change or read the sky of the resident scene alone.  The resident form is the same in every case: 6 x S x S RGBA32F, sampled as
+ * documented at SkyFaces.  All three need an uploaded scene (IDKPT_ERR_INVALID_OPERATION otherwise) and validate everything before anything resident changes.  The two
+ * updates are stream-ordered behind the samples already queued (they are launched first, with the old sky) and do not wait for the GPU — except once when S outgrows the
+ * allocation; the accumulation is the host's to reset, as after any scene update.  A multi-device context keeps one copy per member. */
+typedef struct idkpt_atmosphere { int32_t ISteps, JSteps; float LightIntensity, Azimuth, Elevation; } idkpt_atmosphere;  /* AtmosphericScatterer.GpuSettings (Source/Render/AtmosphericScatterer.cs:9-20), same order; the reference's defaults: 40, 8, 15, 0, 0 */
+/* AtmosphericScatterer.Compute + SkyBoxManager's handle upload: the six faces are computed on the device — Shaders/AtmosphericScattering/compute.glsl restated operation
+ * for operation in binary32 (csrc/kernels_sky.hpp), LightIntensity clamped with max(., 0) first as the reference does — and become the scene's sky; alpha is 1.
+ * faceSize 1..4096 (the reference: 128), ISteps / JSteps 1..4096, the three floats finite; else IDKPT_ERR_INVALID_ARGUMENT.  Every member of a multi-device context
+ * computes its own copy. */
+IDKPT_API int32_t idkptComputeSky(idkpt_ctx* ctx, int32_t faceSize, const idkpt_atmosphere* atmosphere);
+/* externalCubemapTexture.Upload3D x 6 (SkyBoxManager.LoadSkyBoxImages: R8G8B8A8SRgb): host faces replace the sky.  format: IDKPT_TEXFMT_RGBA32F | RGBA8 | SRGB8_A8
+ * (6 * S * S texels, face order +X, -X, +Y, -Y, +Z, -Z, rows as SkyFaces); 8-bit texels are expanded on the device exactly as the texture table decodes them (UNORM c / 255;
+ * sRGB on R, G, B, alpha linear).  faces == NULL or faceSize == 0: no sky (black).  faceSize 0..4096.  A multi-device context uploads once and replicates device to device. */
+IDKPT_API int32_t idkptUpdateSky(idkpt_ctx* ctx, int32_t faceSize, int32_t format, const void* faces);
+/* the resident faces (always RGBA32F): *outFaceSize = S (0: no sky); dst != NULL receives 6 * S * S * 16 bytes (queued samples are launched first and the call synchronises,
+ * like the other Download calls; dstBytes too small: IDKPT_ERR_INVALID_ARGUMENT); dst == NULL only fills outFaceSize.  A multi-device context reads its first member's copy. */
+IDKPT_API int32_t idkptDownloadSky(idkpt_ctx* ctx, int32_t* outFaceSize, float* dst, size_t dstBytes);
 IDKPT_API int32_t idkptSetLightCount(idkpt_ctx* ctx, int32_t count);
 /* BVH.TlasBuild upload (Bvh/BVH.cs:278-298): host-built TLAS nodes replace SSBO 27 */
 IDKPT_API int32_t idkptBuildTlas(idkpt_ctx* ctx, const GpuTlasNode* nodes, int32_t nodeCount);
