@@ -155,6 +155,7 @@ struct dev_ctx {
     DevBuf pmList;                                       // the first bounce's work list in pixel-major order (k_shade_first)
     DevBuf trRec, contFlag, blockSums, rayO, rayT, rayR, aovA, aovN, hit, hitCost, primHit, queue[2], keys[2], keysTmp, sortKeys, sortVals, contMask, waveCounts, counts, work, sortHist, counters64;
     DevBuf img[3];
+    std::vector<DevBuf> disp; std::vector<int> dispFmt;   // idkptPresent: the display image of every ring slot (allocated at the first present of the slot) and its format (enum idkpt_display_format; -1: not presented since the last resize)
     DevBuf camTab;                                       // per-sample cameras of the batch being launched (ring mode)
     int rowLimit = 0x7fffffff;                           // idkptSetRowRange: at most this many local rows
     idkpt_bounce_exchange_fn exchangeFn = nullptr; void* exchangeUser = nullptr;   // exact multi-GPU deep paths (idkptSetBounceExchange)

@@ -29,6 +29,8 @@ static int alloc_frame_impl(dev_ctx* ctx)
     HIPC(hipMemsetAsync(ctx->aovA.p, 0, cap * 16, ctx->stream)); HIPC(hipMemsetAsync(ctx->aovN.p, 0, cap * 16, ctx->stream));
     HIPC(hipMemsetAsync(ctx->contFlag.p, 0, cap, ctx->stream));   // per-batch values are written by k_gen_primary; the pad ids [N, Npad) must read 0
     ctx->accum.assign(ctx->ringSize, 0u); ctx->curSlot = 0; ctx->ringStarted = false;
+    for (DevBuf& b : ctx->disp) b.release();                       // display images (idkptPresent) belong to a frame size and a ring: re-made at their next use
+    ctx->disp.clear(); ctx->dispFmt.clear();
     return IDKPT_OK;
 }
 
@@ -41,7 +43,9 @@ static int alloc_frame_keep_images(dev_ctx* ctx)
     const size_t N = (size_t)ctx->W * ctx->rows;
     DevBuf saved[3];
     for (int i = 0; i < 3; i++) { saved[i] = ctx->img[i]; ctx->img[i] = DevBuf(); }
+    std::vector<DevBuf> disp; std::vector<int> dispFmt; disp.swap(ctx->disp); dispFmt.swap(ctx->dispFmt);   // (the display images stay as well: same size, same ring)
     int rc = alloc_frame(ctx);
+    ctx->disp.swap(disp); ctx->dispFmt.swap(dispFmt);
     // The restore is ordered on the context's stream, behind the zero-fill alloc_frame_impl queued there: the stream is non-blocking, so
     // a null-stream copy would be unordered against that fill (the fill could land after the restore and wipe the accumulation).
     hipError_t e = hipSuccess;

@@ -169,3 +169,77 @@ static int32_t dev_SetStream(dev_ctx* ctx, void* hipStream)
     return IDKPT_OK;
 }
 static int32_t dev_GetStream(dev_ctx* ctx, void** out) { if (!ctx || !out) return IDKPT_ERR_INVALID_ARGUMENT; *out = (void*)ctx->stream; return IDKPT_OK; }
+
+// ---- the display image (idkptPresent / idkptDownloadDisplay / idkptGetDisplayDevicePtr; kernels_present.hpp) ------------------------------------------------------------
+// One buffer per ring slot, allocated at the slot's first present (a context that never presents pays nothing) and released with the frame buffers (alloc_frame_impl).
+// Every buffer ends with DISPLAY_GUARD_BYTES of 0xA5 right behind the image that no kernel writes (include/idkpt.h: what a host or a test can look at to see that a
+// row tail never ran past the image).
+#define DISPLAY_GUARD_BYTES 64
+static size_t display_texel_bytes(int format) { return format == IDKPT_DISPLAY_RGBA32F ? 16 : 4; }
+// everything idkptPresent refuses before anything is launched (shared with the multi-device layer)
+static int32_t present_validate(dev_ctx* ctx, int32_t slot, int32_t image, const idkpt_tonemap* tm, int32_t format)
+{
+    REQUIRE(slot >= -1 && slot < ctx->ringSize, "idkptPresent: slot outside the frame ring (-1: the current slot)");
+    REQUIRE(image >= 0 && image < 3, "idkptPresent: bad image id");
+    REQUIRE(format == IDKPT_DISPLAY_RGBA8 || format == IDKPT_DISPLAY_RGBA32F, "idkptPresent: format must be IDKPT_DISPLAY_RGBA8 or IDKPT_DISPLAY_RGBA32F");
+    auto fin = [](float v) { return v - v == 0.0f; };
+    REQUIRE(fin(tm->Exposure) && fin(tm->Saturation) && fin(tm->Linear) && fin(tm->Peak) && fin(tm->Compression), "idkptPresent: Exposure, Saturation, Linear, Peak and Compression must be finite");
+    if (ctx->W <= 0 || !ctx->frameOk) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptPresent: no frame buffers (idkptSetSize not called)");
+    return IDKPT_OK;
+}
+static int32_t dev_Present(dev_ctx* ctx, int32_t slot, int32_t image, const idkpt_tonemap* tm, int32_t format, const void* dAdd0, const void* dAdd1)
+{
+    if (!ctx || !tm) return IDKPT_ERR_INVALID_ARGUMENT;
+    { int rc = present_validate(ctx, slot, image, tm, format); if (rc) return rc; }
+    if (slot < 0) slot = ctx->curSlot;
+    HIPC(hipSetDevice(ctx->device));
+    FLUSH_KEEP();                                        // stream-ordered behind what was queued; the frame is complete without the deferred bounce's continuation (finish_deferred)
+    { int rc = check_overflow(ctx); if (rc) return rc; }   // (no wait: see idkptGetFrameDevicePtr)
+    const size_t N = (size_t)ctx->W * ctx->rows, imageBytes = N * display_texel_bytes(format);
+    if (ctx->disp.size() != (size_t)ctx->ringSize) { ctx->disp.resize(ctx->ringSize); ctx->dispFmt.assign(ctx->ringSize, -1); }
+    DevBuf& buf = ctx->disp[slot];
+    if (!buf.p || buf.bytes < imageBytes + DISPLAY_GUARD_BYTES) { ctx->dispFmt[slot] = -1; HIPC(buf.ensure(imageBytes + DISPLAY_GUARD_BYTES)); }
+    if (ctx->dispFmt[slot] != format) HIPC(hipMemsetAsync((char*)buf.p + imageBytes, 0xA5, DISPLAY_GUARD_BYTES, ctx->stream));   // (the guard sits right behind the image of THIS format)
+    presentk::Params p;
+    presentk::present_setup(tm->Exposure, tm->Compression, &p);
+    p.saturation = tm->Saturation; p.linear = tm->Linear; p.peak = tm->Peak; p.doTonemap = tm->DoTonemapAndSrgbTransform != 0;
+    p.W = ctx->W; p.rows = ctx->rows; p.rowMod = ctx->rowMod; p.rowRem = ctx->rowRem; p.bandLog2 = ctx->rowBandLog2;
+    const uint32_t threads = (uint32_t)(((size_t)ctx->W + 3) / 4 * ctx->rows);
+    if (threads) {
+        if (format == IDKPT_DISPLAY_RGBA32F) hipLaunchKernelGGL((k_present<true>), dim3((threads + 255u) / 256u), dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, image, slot), (const float4*)dAdd0, (const float4*)dAdd1, buf.p, p);
+        else hipLaunchKernelGGL((k_present<false>), dim3((threads + 255u) / 256u), dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, image, slot), (const float4*)dAdd0, (const float4*)dAdd1, buf.p, p);
+        HIPC(hipGetLastError());
+    }
+    ctx->dispFmt[slot] = format;
+    return IDKPT_OK;
+}
+// the last presented image of a slot: *outFormat its format, *outBytes localRows * width * (4 | 16); INVALID_OPERATION when the slot was not presented since the last resize
+static int32_t display_of(dev_ctx* ctx, const char* who, int32_t slot, int32_t* outSlot, size_t* outBytes)
+{
+    REQUIRE(slot >= -1 && slot < ctx->ringSize, std::string(who) + ": slot outside the frame ring (-1: the current slot)");
+    if (slot < 0) slot = ctx->curSlot;
+    if ((size_t)slot >= ctx->dispFmt.size() || ctx->dispFmt[slot] < 0) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, std::string(who) + ": the slot was not presented since the last resize (idkptPresent)");
+    *outSlot = slot; *outBytes = (size_t)ctx->W * ctx->rows * display_texel_bytes(ctx->dispFmt[slot]);
+    return IDKPT_OK;
+}
+static int32_t dev_DownloadDisplay(dev_ctx* ctx, int32_t slot, void* dst, size_t bytes)
+{
+    if (!ctx || !dst) return IDKPT_ERR_INVALID_ARGUMENT;
+    size_t need = 0;
+    { int rc = display_of(ctx, "idkptDownloadDisplay", slot, &slot, &need); if (rc) return rc; }
+    REQUIRE(bytes == need, "idkptDownloadDisplay: bytes must equal localRows*width*4 (RGBA8) or localRows*width*16 (RGBA32F)");
+    HIPC(hipSetDevice(ctx->device));
+    FLUSH_KEEP();
+    HIPC(hipMemcpyAsync(dst, ctx->disp[slot].p, need, hipMemcpyDeviceToHost, ctx->stream));
+    SYNC_CHECKED();
+    return IDKPT_OK;
+}
+static int32_t dev_GetDisplayDevicePtr(dev_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes)
+{
+    if (!ctx || !outPtr) return IDKPT_ERR_INVALID_ARGUMENT;
+    size_t need = 0;
+    { int rc = display_of(ctx, "idkptGetDisplayDevicePtr", slot, &slot, &need); if (rc) return rc; }
+    *outPtr = ctx->disp[slot].p;
+    if (outBytes) *outBytes = need;
+    return IDKPT_OK;
+}

@@ -129,6 +129,7 @@ static int32_t dev_Destroy(dev_ctx* ctx)
                      &ctx->counts, &ctx->work, &ctx->qwork, &ctx->radSave, &ctx->deferCount, &ctx->sortHist, &ctx->counters64, &ctx->bases, &ctx->img[0], &ctx->img[1], &ctx->img[2]};
     for (DevBuf* b : all) b->release();
     for (auto& t : ctx->texData) t.release();
+    for (DevBuf& b : ctx->disp) b.release();
     builder_scratch_free(ctx);
     if (ctx->hCounts) (void)hipHostFree(ctx->hCounts);
     if (ctx->hOverflow) (void)hipHostFree(ctx->hOverflow);

@@ -33,6 +33,7 @@ using namespace ptd;
 #include "kernels_scene.hpp"
 #include "kernels_texture.hpp"
 #include "kernels_sky.hpp"
+#include "kernels_present.hpp"
 #include "bvh_gpu.hpp"
 #include "bvh_gpu_full.hpp"
 

@@ -96,7 +96,7 @@ struct idkpt_ctx {
     std::vector<DevBuf> peerStage, gbase;                   // on member d: the lower members' per-sample bases of the current bounce; the summed slot bases
     GroupWorkers workers;                                   // one enqueuing thread per member (threaded flushes)
     GroupBarrier bar; std::vector<GroupBandUser> bandUser; std::vector<std::vector<uint32_t>> bandCounts; std::vector<int> bandLB;   // interleaved layouts beyond RayDepth 2 (group_band_exchange)
-    DevBuf full[3], gatherStage, rowOffDev;                 // on device 0: gathered full-frame images; landing zone of the interleaved rows; first landing row of every member
+    DevBuf full[3], fullDisp, gatherStage, rowOffDev;       // on device 0: gathered full-frame images / display image; landing zone of the interleaved rows; first landing row of every member
     size_t n() const { return dev.size(); }
 };
 
@@ -111,7 +111,9 @@ __global__ void k_group_bases(const uint32_t* stage, int lower, int stride, int 
 }
 // full[y][x] = rows of member (y >> bandLog2) % n, landed contiguously per member in `stage` (member d at rowOffset[d] rows; its local row of image row y:
 // band (y >> bandLog2) / n of the member, row y & (band - 1) inside it — every band but the image's last is complete)
-__global__ void k_interleave_rows(const float4* stage, float4* full, int W, int H, int n, const int* rowOffset, int bandLog2)
+// T: one texel — float4 (the RGBA32F images and displays) or uint32_t (the RGBA8 display)
+template <class T>
+__global__ void k_interleave_rows(const T* stage, T* full, int W, int H, int n, const int* rowOffset, int bandLog2)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t)W * H) return;
@@ -278,18 +280,15 @@ static int group_layout(idkpt_ctx* c, int W, int H)
 }
 
 // member rows -> host image (every member copies its rows itself: one PCIe link per GPU)
-static int group_download_image(idkpt_ctx* c, int image, int slot, float* rgba, size_t bytes)
+// (srcs[d]: member d's rows, texelBytes per texel: 16 for the RGBA32F images and displays, 4 for the RGBA8 display)
+static int group_download_rows(idkpt_ctx* c, const std::vector<const void*>& srcs, size_t texelBytes, void* rgba)
 {
-    GREQ(image >= 0 && image < 3, "idkptDownload: bad image id");
-    const size_t rowBytes = (size_t)c->W * 16;
-    GREQ(c->W > 0 && bytes == rowBytes * c->H, "idkptDownload: bytes must equal height*width*16 (the whole frame of a multi-device context)");
-    GREQ(slot >= 0 && slot < c->dev[0]->ringSize, "idkptDownloadFrame: slot outside the frame ring");
-    GFLUSH();
+    const size_t rowBytes = (size_t)c->W * texelBytes;
     const int n = (int)c->n();
     for (int d = 0; d < n; d++) {
         dev_ctx* m = c->dev[d];
         GHIP(hipSetDevice(m->device));
-        const float4* src = image_ptr(m, image, slot);
+        const void* src = srcs[d];
         if (c->strips) GHIP(hipMemcpyAsync((char*)rgba + (size_t)c->firstRow[d] * rowBytes, src, (size_t)m->rows * rowBytes, hipMemcpyDeviceToHost, m->stream));
         else {
             // band k of this member = band k * n + d of the image: one 2D copy whose "rows" are whole bands, plus the member's last band when the image cuts it short
@@ -300,18 +299,26 @@ static int group_download_image(idkpt_ctx* c, int image, int slot, float* rgba, 
     }
     return group_sync(c);
 }
+static int group_download_image(idkpt_ctx* c, int image, int slot, float* rgba, size_t bytes)
+{
+    GREQ(image >= 0 && image < 3, "idkptDownload: bad image id");
+    GREQ(c->W > 0 && bytes == (size_t)c->W * 16 * c->H, "idkptDownload: bytes must equal height*width*16 (the whole frame of a multi-device context)");
+    GREQ(slot >= 0 && slot < c->dev[0]->ringSize, "idkptDownloadFrame: slot outside the frame ring");
+    GFLUSH();
+    std::vector<const void*> srcs;
+    for (dev_ctx* m : c->dev) srcs.push_back(image_ptr(m, image, slot));
+    return group_download_rows(c, srcs, 16, rgba);
+}
 
 // member rows -> full frame on device 0 (RCCL send / recv, or peer copies; interleaved rows land in a staging area and are woven together by one kernel)
-static int group_gather_device(idkpt_ctx* c, int image, int slot, void** outPtr, size_t* outBytes)
+// (srcs[d]: member d's rows, texelBytes per texel — 16 or 4 —, full: the buffer of device 0 that receives the frame)
+static int group_gather_rows(idkpt_ctx* c, const std::vector<const void*>& srcs, size_t texelBytes, DevBuf& full, void** outPtr, size_t* outBytes)
 {
-    GREQ(image >= 0 && image < 3 && c->W > 0, "idkptGetImageDevicePtr: bad image / no size");
-    GREQ(slot >= 0 && slot < c->dev[0]->ringSize, "idkptGetFrameDevicePtr: slot outside the frame ring");
-    GFLUSH();
     const int n = (int)c->n();
-    const size_t rowBytes = (size_t)c->W * 16, frameBytes = rowBytes * c->H;
+    const size_t rowBytes = (size_t)c->W * texelBytes, frameBytes = rowBytes * c->H;
     dev_ctx* m0 = c->dev[0];
     GHIP(hipSetDevice(m0->device));
-    GHIP(c->full[image].ensure(frameBytes));
+    GHIP(full.ensure(frameBytes));
     std::vector<int> rowOff(n + 1, 0);
     for (int d = 0; d < n; d++) rowOff[d + 1] = rowOff[d] + c->dev[d]->rows;
     if (!c->strips) GHIP(c->gatherStage.ensure(frameBytes));
@@ -325,8 +332,8 @@ static int group_gather_device(idkpt_ctx* c, int image, int slot, void** outPtr,
         std::vector<const void*> src(n); std::vector<void*> dst(n); std::vector<size_t> bytes(n); std::vector<int> devs(n); std::vector<hipStream_t> streams(n);
         for (int d = 0; d < n; d++) {
             dev_ctx* m = c->dev[d];
-            src[d] = image_ptr(m, image, slot); bytes[d] = (size_t)m->rows * rowBytes; devs[d] = m->device; streams[d] = m->stream;
-            dst[d] = c->strips ? (char*)c->full[image].p + (size_t)c->firstRow[d] * rowBytes : (char*)c->gatherStage.p + (size_t)rowOff[d] * rowBytes;
+            src[d] = srcs[d]; bytes[d] = (size_t)m->rows * rowBytes; devs[d] = m->device; streams[d] = m->stream;
+            dst[d] = c->strips ? (char*)full.p + (size_t)c->firstRow[d] * rowBytes : (char*)c->gatherStage.p + (size_t)rowOff[d] * rowBytes;
             if (d > 0) { GHIP(hipSetDevice(m->device)); GHIP(hipStreamWaitEvent(m->stream, c->evGatherStart, 0)); }
         }
         GHIP(hipSetDevice(m0->device));
@@ -339,19 +346,39 @@ static int group_gather_device(idkpt_ctx* c, int image, int slot, void** outPtr,
         dev_ctx* m = c->dev[d];
         GHIP(hipSetDevice(m->device));
         GHIP(hipStreamWaitEvent(m->stream, c->evGatherStart, 0));
-        char* dst = c->strips ? (char*)c->full[image].p + (size_t)c->firstRow[d] * rowBytes : (char*)c->gatherStage.p + (size_t)rowOff[d] * rowBytes;
-        GHIP(member_copy(&c->peer, dst, m0->device, image_ptr(m, image, slot), m->device, (size_t)m->rows * rowBytes, m->stream));   // ordered behind the member's FinalDraw
+        char* dst = c->strips ? (char*)full.p + (size_t)c->firstRow[d] * rowBytes : (char*)c->gatherStage.p + (size_t)rowOff[d] * rowBytes;
+        GHIP(member_copy(&c->peer, dst, m0->device, srcs[d], m->device, (size_t)m->rows * rowBytes, m->stream));   // ordered behind the member's FinalDraw
         GHIP(hipEventRecord(c->evGather[d], m->stream));
     }
     GHIP(hipSetDevice(m0->device));
     for (int d = 1; d < n; d++) GHIP(hipStreamWaitEvent(m0->stream, c->evGather[d], 0));
     if (!c->strips) {
         const size_t px = (size_t)c->W * c->H;
-        hipLaunchKernelGGL(k_interleave_rows, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, m0->stream, (const float4*)c->gatherStage.p, (float4*)c->full[image].p, c->W, c->H, n, (const int*)c->rowOffDev.p, c->bandLog2);
+        if (texelBytes == 16) hipLaunchKernelGGL((k_interleave_rows<float4>), dim3((unsigned)((px + 255) / 256)), dim3(256), 0, m0->stream, (const float4*)c->gatherStage.p, (float4*)full.p, c->W, c->H, n, (const int*)c->rowOffDev.p, c->bandLog2);
+        else hipLaunchKernelGGL((k_interleave_rows<uint32_t>), dim3((unsigned)((px + 255) / 256)), dim3(256), 0, m0->stream, (const uint32_t*)c->gatherStage.p, (uint32_t*)full.p, c->W, c->H, n, (const int*)c->rowOffDev.p, c->bandLog2);
         GHIP(hipGetLastError());
     }
-    *outPtr = c->full[image].p;
+    *outPtr = full.p;
     if (outBytes) *outBytes = frameBytes;
+    return IDKPT_OK;
+}
+static int group_gather_device(idkpt_ctx* c, int image, int slot, void** outPtr, size_t* outBytes)
+{
+    GREQ(image >= 0 && image < 3 && c->W > 0, "idkptGetImageDevicePtr: bad image / no size");
+    GREQ(slot >= 0 && slot < c->dev[0]->ringSize, "idkptGetFrameDevicePtr: slot outside the frame ring");
+    GFLUSH();
+    std::vector<const void*> srcs;
+    for (dev_ctx* m : c->dev) srcs.push_back(image_ptr(m, image, slot));
+    return group_gather_rows(c, srcs, 16, c->full[image], outPtr, outBytes);
+}
+// the display image (idkptPresent): every member presented its own rows; *outTexel = 4 (RGBA8) or 16 (RGBA32F)
+static int group_display_rows(idkpt_ctx* c, const char* who, int slot, std::vector<const void*>& srcs, size_t* outTexel)
+{
+    for (dev_ctx* m : c->dev) {
+        int s = 0; size_t bytes = 0;
+        int rc = display_of(m, who, slot, &s, &bytes); if (rc) return mfail(c, m, rc);
+        srcs.push_back(m->disp[s].p); *outTexel = display_texel_bytes(m->dispFmt[s]);
+    }
     return IDKPT_OK;
 }
 
@@ -423,6 +450,7 @@ int32_t idkptDestroy(idkpt_ctx* c)
         }
         (void)hipSetDevice(c->dev[0]->device);
         for (int i = 0; i < 3; i++) c->full[i].release();
+        c->fullDisp.release();
         c->gatherStage.release(); c->rowOffDev.release();
         if (c->evGatherStart) (void)hipEventDestroy(c->evGatherStart);
         if (c->peer.stage) (void)hipHostFree(c->peer.stage);
@@ -760,6 +788,38 @@ int32_t idkptGetFrameDevicePtr(idkpt_ctx* c, int32_t slot, int32_t image, void**
     if (!c || !outPtr) return IDKPT_ERR_INVALID_ARGUMENT;
     ONE(dev_GetFrameDevicePtr(m, slot, image, outPtr, outBytes));
     return group_gather_device(c, image, slot, outPtr, outBytes);
+}
+
+// ---- the display image: every member presents its own rows (the dither is indexed with image rows: k_present), downloads and gathers are those of the images
+int32_t idkptPresent(idkpt_ctx* c, int32_t slot, int32_t image, const idkpt_tonemap* tonemap, int32_t format, const void* dAdd0, const void* dAdd1)
+{
+    if (!c || !tonemap) return IDKPT_ERR_INVALID_ARGUMENT;
+    ONE(dev_Present(m, slot, image, tonemap, format, dAdd0, dAdd1));
+    { int rc = present_validate(c->dev[0], slot, image, tonemap, format); if (rc) return mfail(c, c->dev[0], rc); }
+    if (!c->frameOk) return gfail(c, IDKPT_ERR_INVALID_OPERATION, "idkptPresent: no frame buffers (the last re-layout of the devices failed)");
+    if (dAdd0 || dAdd1) return gfail(c, IDKPT_ERR_INVALID_OPERATION, "idkptPresent: device pointers belong to one device; a multi-device context takes no added images");
+    GFLUSH();
+    ALL(dev_Present(m, slot, image, tonemap, format, nullptr, nullptr));
+    (void)hipSetDevice(c->dev[0]->device);
+    return IDKPT_OK;
+}
+int32_t idkptDownloadDisplay(idkpt_ctx* c, int32_t slot, void* dst, size_t bytes)
+{
+    if (!c || !dst) return IDKPT_ERR_INVALID_ARGUMENT;
+    ONE(dev_DownloadDisplay(m, slot, dst, bytes));
+    std::vector<const void*> srcs; size_t texel = 0;
+    { int rc = group_display_rows(c, "idkptDownloadDisplay", slot, srcs, &texel); if (rc) return rc; }
+    GREQ(bytes == (size_t)c->W * c->H * texel, "idkptDownloadDisplay: bytes must equal height*width*4 (RGBA8) or height*width*16 (RGBA32F): the whole frame of a multi-device context");
+    GFLUSH();
+    return group_download_rows(c, srcs, texel, dst);
+}
+int32_t idkptGetDisplayDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size_t* outBytes)
+{
+    if (!c || !outPtr) return IDKPT_ERR_INVALID_ARGUMENT;
+    ONE(dev_GetDisplayDevicePtr(m, slot, outPtr, outBytes));
+    std::vector<const void*> srcs; size_t texel = 0;
+    { int rc = group_display_rows(c, "idkptGetDisplayDevicePtr", slot, srcs, &texel); if (rc) return rc; }
+    return group_gather_rows(c, srcs, texel, c->fullDisp, outPtr, outBytes);
 }
 
 int32_t idkptResetAccumulation(idkpt_ctx* c) { if (!c) return IDKPT_ERR_INVALID_ARGUMENT; for (dev_ctx* m : c->dev) dev_ResetAccumulation(m); return IDKPT_OK; }

@@ -253,6 +253,13 @@ class GpuShardRenderer:
         self.pt.frame_device_ptr(first_slot + count - 1, 0)       # raises if the group runs past the end of the ring (slots must be consecutive)
         return torch.as_tensor(_DevArray(ptr, (count, self.rows, self.width, 4)), device=self.device)
 
+    def local_display(self, settings=None, image=0):
+        """idkptPresent (RGBA8) of this rank's rows of the current frame as a (rows, W, 4) uint8 tensor aliasing the library's display buffer; the dither uses the rows'
+        numbers in the whole image, so the gathered display equals the one-GPU display bit for bit."""
+        ptr, nbytes = self.pt.present_device_ptr(settings, image)
+        assert nbytes == self.rows * self.width * 4
+        return torch.as_tensor(_DevArray(ptr, (self.rows, self.width, 4), "|u1"), device=self.device)
+
     def local_image(self):
         self.pt.flush()   # launch whatever the library still defers; the collective that follows is stream-ordered behind it
         ptr, nbytes = self.pt.image_device_ptr(0)
@@ -323,8 +330,19 @@ class ShardedFrame:
                 idx = torch.tensor(rows, dtype=torch.long, device=full.device); self._row_index[(r, str(full.device))] = idx
             full.index_copy_(dim, idx, part[sel + (slice(0, n),)])
 
-    def _gather(self):
-        local = self.r.local_image()
+    def gather_display(self, *args, **kwargs):
+        """All-gather of the ranks' DISPLAY rows (renderer.local_display(...): uint8 RGBA8, what idkptPresent produced for this rank's rows — 4 bytes per pixel, a quarter
+        of gather()'s traffic); same padding and placement as gather().  Returns the full (H, W, 4) uint8 image on every rank."""
+        import contextlib
+        ctx = self.r.stream_ctx() if hasattr(self.r, "stream_ctx") else contextlib.nullcontext()
+        with ctx:
+            local = self.r.local_display(*args, **kwargs)
+            assert local.dtype == torch.uint8 and tuple(local.shape) == (len(self.rank_rows[self.rank]), self.width, 4)
+            return self._gather(local)
+
+    def _gather(self, local=None):
+        if local is None:
+            local = self.r.local_image()
         if local.shape[0] < self.max_rows:  # ranks with one row less pad (all_gather needs equal shapes)
             pad = torch.zeros((self.max_rows - local.shape[0],) + tuple(local.shape[1:]), dtype=local.dtype, device=local.device)
             local = torch.cat([local, pad], dim=0)
@@ -334,6 +352,9 @@ class ShardedFrame:
         for r in range(self.world):
             self._place(full, parts[r], r, 0)
         return full
+
+
+FrameGatherer = ShardedFrame   # (the name hosts know the gathering half by: gather(), gather_frames(), gather_display())
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -167,6 +167,17 @@ class Atmosphere(C.Structure):
         super().__init__(int(ISteps), int(JSteps), float(LightIntensity), float(Azimuth), float(Elevation))
 
 
+class TonemapSettings(C.Structure):
+    """idkpt_tonemap = TonemapAndGammaCorrect.GpuSettings (Source/Render/TonemapAndGammaCorrecter.cs:10-22), same order; the defaults are the reference's."""
+    _fields_ = [("Exposure", C.c_float), ("Saturation", C.c_float), ("Linear", C.c_float), ("Peak", C.c_float), ("Compression", C.c_float), ("DoTonemapAndSrgbTransform", C.c_int32)]
+
+    def __init__(self, Exposure=0.45, Saturation=1.06, Linear=0.18, Peak=1.0, Compression=0.1, DoTonemapAndSrgbTransform=True):
+        super().__init__(float(Exposure), float(Saturation), float(Linear), float(Peak), float(Compression), 1 if DoTonemapAndSrgbTransform else 0)
+
+
+IDKPT_DISPLAY_RGBA8, IDKPT_DISPLAY_RGBA32F = 0, 1
+
+
 class Stats(C.Structure):
     _fields_ = [("RaysTraced", C.c_uint64), ("PrimaryRays", C.c_uint64), ("Frames", C.c_uint64),
                 ("LastAliveCounts", C.c_uint32 * 16), ("LastTraceMs", C.c_float), ("LastFrameMs", C.c_float),

@@ -415,6 +415,35 @@ class PathTracer:
             self._check(self._L.idkptDownloadSky(self._ctx, C.byref(s), out.ctypes.data, out.nbytes))
         return out
 
+    # ---- display output (idkptPresent / idkptDownloadDisplay / idkptGetDisplayDevicePtr): TonemapAndGammaCorrect.Compute on the device
+    def _present(self, settings, image, slot, fmt):
+        formats = {"rgba8": T.IDKPT_DISPLAY_RGBA8, "rgba32f": T.IDKPT_DISPLAY_RGBA32F}
+        if fmt not in formats:
+            raise ValueError(f"Present: fmt must be 'rgba8' or 'rgba32f', got {fmt!r}")
+        if settings is None:
+            settings = T.TonemapSettings(DoTonemapAndSrgbTransform=not self.DoDebugBVHTraversal)     # Application.cs:222
+        if not isinstance(settings, T.TonemapSettings):
+            raise TypeError("Present: settings must be a gputypes.TonemapSettings")
+        slot = -1 if slot is None else int(slot)
+        self._check(self._L.idkptPresent(self._ctx, slot, int(image), C.addressof(settings), formats[fmt], None, None))
+        return slot, formats[fmt]
+
+    def Present(self, settings=None, image=0, slot=None, fmt="rgba8"):
+        """TonemapAndGamma.Compute(PathTracer.Result) + the download of its R8G8B8A8Unorm result: the tone-mapped, sRGB-encoded, dithered image of `image` (0-2) of ring
+        slot `slot` (None: the current one) as an (H, W, 4) numpy array — uint8 for fmt "rgba8", float32 (the value before quantisation) for "rgba32f".  settings: a
+        gputypes.TonemapSettings; None = the reference's defaults with DoTonemapAndSrgbTransform = not DoDebugBVHTraversal, as Application.cs:222 sets it."""
+        slot, f = self._present(settings, image, slot, fmt)
+        out = np.zeros((self.rows, self.width, 4), np.float32 if f == T.IDKPT_DISPLAY_RGBA32F else np.uint8)
+        self._check(self._L.idkptDownloadDisplay(self._ctx, slot, out.ctypes.data, out.nbytes))
+        return out
+
+    def present_device_ptr(self, settings=None, image=0, slot=None, fmt="rgba8"):
+        """idkptPresent + idkptGetDisplayDevicePtr: (device pointer, bytes) of the display image, valid in stream order; nothing is downloaded or waited for."""
+        slot, _ = self._present(settings, image, slot, fmt)
+        p = C.c_void_p(); n = C.c_size_t()
+        self._check(self._L.idkptGetDisplayDevicePtr(self._ctx, slot, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
     def enable_counters(self, on=True):
         self._check(self._L.idkptEnableCounters(self._ctx, 1 if on else 0))
 

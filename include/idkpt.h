@@ -196,10 +196,10 @@ typedef struct idkpt_stats {
     uint32_t InstUnifiedTopDepth;  /* depth of that top */
 } idkpt_stats;
 /* The layout above only ever GROWS at its end, and IDKPT_ABI_VERSION counts the growths (and every other change a host compiled against an older header could trip over: new
- * enum values of idkpt_buffer or idkpt_texture_format, new fields of idkpt_texture, new entry points: 5 = idkptComputeSky / idkptUpdateSky / idkptDownloadSky).  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
+ * enum values of idkpt_buffer or idkpt_texture_format, new fields of idkpt_texture, new entry points: 5 = idkptComputeSky / idkptUpdateSky / idkptDownloadSky, 6 = idkptPresent / idkptDownloadDisplay / idkptGetDisplayDevicePtr).  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
  * of ITS struct to idkptGetStatsSized and gets exactly that many bytes; idkptGetStats(ctx, out) is idkptGetStatsSized(ctx, out, sizeof(idkpt_stats)) of the header the LIBRARY
  * was built with — for hosts built from the same tree.  idkptGetAbiVersion() lets a host refuse a library older than the header it was written against. */
-#define IDKPT_ABI_VERSION 5
+#define IDKPT_ABI_VERSION 6
 
 /* ---- lifetime --------------------------------------------------------------------------- */
 /* new PathTracer(w,h,settings) (PathTracer.cs:170-212).  deviceCount = 1: the reference's situation, one GPU.
@@ -431,6 +431,35 @@ IDKPT_API int32_t idkptSetFrameRing(idkpt_ctx* ctx, int32_t frames);
 IDKPT_API int32_t idkptBeginFrame(idkpt_ctx* ctx, int32_t* outSlot);
 IDKPT_API int32_t idkptDownloadFrame(idkpt_ctx* ctx, int32_t slot, int32_t image, float* rgba, size_t bytes);
 IDKPT_API int32_t idkptGetFrameDevicePtr(idkpt_ctx* ctx, int32_t slot, int32_t image, void** outPtr, size_t* outBytes);
+
+/* ---- display output (ABI 6): TonemapAndGammaCorrect.Compute (Source/Render/TonemapAndGammaCorrecter.cs, Shaders/TonemapAndGammaCorrect/compute.glsl) -------------------
+ * The one pass between PathTracer.Result and the swapchain (Source/Application.cs:217-223): AgX tonemap, sRGB transfer and the 8 x 8 Bayer dither, run on the device so
+ * that a displayed frame leaves it as 4 bytes per pixel instead of 16.  Bloom (the shader's Sampler1 / Sampler2 come from the host) and resampling to another
+ * presentation size stay with the host: the display image has the render size. */
+typedef struct idkpt_tonemap { float Exposure, Saturation, Linear, Peak, Compression; int32_t DoTonemapAndSrgbTransform; } idkpt_tonemap;
+/* TonemapAndGammaCorrect.GpuSettings, same order; the reference's defaults 0.45, 1.06, 0.18, 1.0, 0.1, 1.  DoTonemapAndSrgbTransform = 0 is the reference's
+ * DoDebugBVHTraversal path (Application.cs:222): clamp to [0, 1], no sRGB, dither. */
+enum idkpt_display_format { IDKPT_DISPLAY_RGBA8 = 0 /* the reference's R8G8B8A8Unorm */, IDKPT_DISPLAY_RGBA32F = 1 /* the value imageStore receives, before quantisation */ };
+/* Produces the display image of ring slot `slot` (-1: the current slot) from image `image` (enum idkpt_image) of that slot.  Stream-ordered behind what is queued: queued
+ * samples are launched first (as idkptGetFrameDevicePtr does) and the call does not wait for the GPU.  dAdd0 / dAdd1: optional device pointers to RGBA32F images of the
+ * context's size (localRows * width texels) — the host's bloom, the shader's Sampler1 / Sampler2; the sum is formed in the shader's order ((0 + s0) + s1) + s2, and NULL
+ * contributes the + 0.0 an unbound GL texture does.  A multi-device context presents on every member (each its own rows, dithered with the rows' numbers in the whole
+ * image, so the result equals the one-device display bit for bit) and takes no added images: both pointers must be NULL there (IDKPT_ERR_INVALID_OPERATION).
+ * The arithmetic is the shader's, operation for operation in binary32 (csrc/kernels_present.hpp); inverse(mat3), exp and pow are implementation-defined in GLSL, so the
+ * result is held to a measured bound against the formula's binary64 value, not to a GL driver bit for bit (tests/test_present_ref.py, profiles/present.md).
+ * Quantisation (the contract): IDKPT_DISPLAY_RGBA8 holds byte = (uint8) rintf(fminf(fmaxf(x, 0), 1) * 255.0f) per channel — round to nearest, ties to even — in memory
+ * order R, G, B, A with alpha 255; IDKPT_DISPLAY_RGBA32F holds (dithered.rgb, 1.0).  The dither is BayerMatrix8[x % 8][y % 8] with y the row of the whole image.
+ * Display buffers are allocated per slot at the slot's first present and re-made by idkptSetSize / idkptSetFrameRing (and everything else that re-makes the images:
+ * the row layout calls); a context that never presents pays nothing.  Every buffer ends with 64 guard bytes of value 0xA5 directly behind the image, which nothing writes.
+ * Validated before anything is launched: slot and image in range, format known, the five floats finite (IDKPT_ERR_INVALID_ARGUMENT); no size set: IDKPT_ERR_INVALID_OPERATION. */
+IDKPT_API int32_t idkptPresent(idkpt_ctx* ctx, int32_t slot, int32_t image, const idkpt_tonemap* tonemap, int32_t format, const void* dAdd0, const void* dAdd1);
+/* The last presented image of a slot (-1: the current slot): localRows * width * 4 bytes (RGBA8) or * 16 bytes (RGBA32F) — of the whole frame on a multi-device context —
+ * and `bytes` must match (IDKPT_ERR_INVALID_ARGUMENT).  IDKPT_ERR_INVALID_OPERATION if the slot was not presented since the last resize.  idkptDownloadDisplay synchronises
+ * like the other Download calls (on a multi-device context every member copies its rows into the host image itself); idkptGetDisplayDevicePtr does not wait: the pointer is
+ * valid in stream order (idkptGetStream) until the next present of that slot or resize; a multi-device context gathers the rows on its first device as
+ * idkptGetFrameDevicePtr does (RCCL or peer copies), 4 bytes per pixel for RGBA8. */
+IDKPT_API int32_t idkptDownloadDisplay(idkpt_ctx* ctx, int32_t slot, void* dst, size_t bytes);
+IDKPT_API int32_t idkptGetDisplayDevicePtr(idkpt_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes);
 
 /* ---- render ----------------------------------------------------------------------------- */
 /* PathTracer.ResetAccumulation (PathTracer.cs:334-337) */
