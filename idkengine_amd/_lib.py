@@ -17,6 +17,7 @@ SYMBOLS = [
     "idkptGetStats", "idkptGetStatsSized", "idkptResetStats", "idkptEnableCounters", "idkptEnableTiming", "idkptGetImageDevicePtr",
     "idkptSetStream", "idkptGetStream", "idkptSetDeveloperOption", "idkptSetMaxBatch", "idkptFlush", "idkptTraceRays", "idkptTraceShadows", "idkptTraceRaysDevice", "idkptTraceShadowsDevice", "idkptSetFrameRing", "idkptBeginFrame", "idkptDownloadFrame", "idkptGetFrameDevicePtr",
     "idkptPresent", "idkptDownloadDisplay", "idkptGetDisplayDevicePtr",
+    "idkptBloom", "idkptGetBloomInfo", "idkptDownloadBloom", "idkptGetBloomDevicePtr",
 ]
 
 _lib = None
@@ -44,6 +45,7 @@ def load():
         "idkptUpdateBuffer": [vp, i32, sz, sz, vp], "idkptUpdateTexture": [vp, i32, vp], "idkptDownloadTexture": [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), vp, sz], "idkptComputeSky": [vp, i32, vp], "idkptUpdateSky": [vp, i32, i32, vp], "idkptDownloadSky": [vp, C.POINTER(i32), vp, sz], "idkptSetLightCount": [vp, i32], "idkptBuildTlas": [vp, vp, i32], "idkptBuildTlasOnDevice": [vp, i32], "idkptBuildBlasCore": [vp, vp, i32, vp, vp, vp], "idkptBuildBlas": [vp, vp, i32, vp, i32, i32, C.c_float, vp], "idkptBuildBlasFetch": [vp, vp, vp, vp, vp], "idkptCbrtProbe": [vp, vp, vp, i32], "idkptTraceRays": [vp, vp, sz, u32, vp], "idkptTraceShadows": [vp, vp, vp, vp, vp], "idkptTraceRaysDevice": [vp, vp, sz, u32, vp], "idkptTraceShadowsDevice": [vp, vp, vp, vp, vp], "idkptSetFrameRing": [vp, i32], "idkptBeginFrame": [vp, C.POINTER(i32)],
         "idkptDownloadFrame": [vp, i32, i32, vp, sz], "idkptGetFrameDevicePtr": [vp, i32, i32, C.POINTER(vp), C.POINTER(sz)],
         "idkptPresent": [vp, i32, i32, vp, i32, vp, vp], "idkptDownloadDisplay": [vp, i32, vp, sz], "idkptGetDisplayDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(sz)],
+        "idkptBloom": [vp, i32, i32, vp], "idkptGetBloomInfo": [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)], "idkptDownloadBloom": [vp, i32, i32, i32, vp, sz], "idkptGetBloomDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(sz)],
         "idkptRefitBlas": [vp, i32], "idkptUploadUnskinnedVertices": [vp, vp, i32], "idkptSkin": [vp, u32, u32, u32, u32],
         "idkptDownloadBuffer": [vp, i32, sz, sz, vp], "idkptResetAccumulation": [vp], "idkptSetSampleSequence": [vp, u32, u32], "idkptGetAccumulatedSamples": [vp, C.POINTER(u32)],
         "idkptRender": [vp], "idkptSynchronize": [vp], "idkptDownload": [vp, i32, vp, sz], "idkptDownloadRays": [vp, vp, sz],

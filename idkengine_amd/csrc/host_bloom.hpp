@@ -1,0 +1,115 @@
+// host_bloom.hpp — idkptBloom / idkptGetBloomInfo / idkptDownloadBloom / idkptGetBloomDevicePtr: Bloom.Compute (Source/Render/Bloom.cs:56-127) on the device
+// (kernels: kernels_bloom.hpp).  Part of the single translation unit idkpt.hip (included there, in this order).
+// Behaves as idkptPresent does (host_readback.hpp): queued samples are launched first, nothing waits for the GPU, buffers belong to a ring slot and a frame size —
+// three per slot (the down chain, the up chain: RGBA16F levels one behind the other; the expanded RGBA32F image), allocated at the slot's first bloom, released by
+// alloc_frame_impl, kept by idkptSetMaxBatch, each followed by BLOOM_GUARD_BYTES of 0xA5 that nothing writes.
+// One device, the whole frame: bloom is a global filter (the last level mixes the whole image), a shard of the rows would need halos as wide as the chain.
+#pragma once
+
+#define BLOOM_GUARD_BYTES 64
+static size_t bloom_level_texels(int w0, int h0, int level) { return (size_t)bloomt::level_dim(w0, level) * (size_t)bloomt::level_dim(h0, level); }
+static size_t bloom_level_offset(int w0, int h0, int level) { size_t t = 0; for (int l = 0; l < level; l++) t += bloom_level_texels(w0, h0, l); return t; }   // texels in front of `level`
+// k_bloom_down0 stages SRC_TILE source texels per axis: true when every tile of a level of `dsize` texels reading `ssize` texels stays inside
+static bool bloom_tile_spans_fit(int dsize, int ssize)
+{
+    for (int t0 = 0; t0 < dsize; t0 += bloomk::TILE) {
+        int lo, hi; bloomk::tap_range(t0, std::min(t0 + bloomk::TILE - 1, dsize - 1), dsize, ssize, 2, &lo, &hi);
+        if (hi - lo + 1 > bloomk::SRC_TILE) return false;
+    }
+    return true;
+}
+static int bloom_ensure(dev_ctx* ctx, DevBuf& buf, size_t& have, size_t bytes)
+{
+    if (buf.p && have == bytes) return IDKPT_OK;
+    HIPC(buf.ensure(bytes + BLOOM_GUARD_BYTES));
+    HIPC(hipMemsetAsync((char*)buf.p + bytes, 0xA5, BLOOM_GUARD_BYTES, ctx->stream));
+    have = bytes;
+    return IDKPT_OK;
+}
+
+static int32_t dev_Bloom(dev_ctx* ctx, int32_t slot, int32_t image, const idkpt_bloom* b)
+{
+    if (!ctx || !b) return IDKPT_ERR_INVALID_ARGUMENT;
+    REQUIRE(slot >= -1 && slot < ctx->ringSize, "idkptBloom: slot outside the frame ring (-1: the current slot)");
+    REQUIRE(image >= 0 && image < 3, "idkptBloom: bad image id");
+    auto fin = [](float v) { return v - v == 0.0f; };
+    REQUIRE(fin(b->Threshold) && fin(b->MaxColor), "idkptBloom: Threshold and MaxColor must be finite");
+    REQUIRE(b->MinusLods >= 0, "idkptBloom: MinusLods must not be negative");
+    if (ctx->W <= 0 || !ctx->frameOk) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptBloom: no frame buffers (idkptSetSize not called)");
+    if (ctx->rowMod != 1 || ctx->rowRem != 0 || ctx->rows != ctx->H) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptBloom: the context holds a shard of the rows (idkptSetRowSharding / idkptSetRowBands / idkptSetRowRange); bloom needs the whole frame on one device");
+    if (ctx->W < 2 || ctx->H < 2) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptBloom: the frame must be at least 2 x 2 (level 0 is width / 2 x height / 2)");
+    if (slot < 0) slot = ctx->curSlot;
+    const int W = ctx->W, H = ctx->H;
+    int w0 = 0, h0 = 0;
+    const int levels = bloomt::bloom_levels(W, H, b->MinusLods, &w0, &h0);
+    if (!bloom_tile_spans_fit(w0, W) || !bloom_tile_spans_fit(h0, H)) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptBloom: internal: a tile of down pass 0 reads more source texels than it stages");
+    HIPC(hipSetDevice(ctx->device));
+    FLUSH_KEEP();                                        // stream-ordered behind what was queued (as idkptPresent)
+    { int rc = check_overflow(ctx); if (rc) return rc; }   // (no wait: see idkptGetFrameDevicePtr)
+    if (ctx->bloom.size() != (size_t)ctx->ringSize) { for (BloomSlot& s : ctx->bloom) s.release(); ctx->bloom.assign(ctx->ringSize, BloomSlot()); }
+    BloomSlot& s = ctx->bloom[slot];
+    s.valid = false;
+    { int rc = bloom_ensure(ctx, s.down, s.downBytes, bloom_level_offset(w0, h0, levels) * 8); if (rc) return rc; }
+    { int rc = bloom_ensure(ctx, s.up, s.upBytes, bloom_level_offset(w0, h0, levels - 1) * 8); if (rc) return rc; }
+    { int rc = bloom_ensure(ctx, s.out, s.outBytes, (size_t)W * H * 16); if (rc) return rc; }
+    auto lvl = [&](DevBuf& buf, int l) { return (uint2*)buf.p + bloom_level_offset(w0, h0, l); };
+    auto dim = [](int d0, int l) { return bloomt::level_dim(d0, l); };
+    auto grid = [](int w, int h) { return dim3((unsigned)((w + bloomk::TILE - 1) / bloomk::TILE), (unsigned)((h + bloomk::TILE - 1) / bloomk::TILE)); };
+    // down pass 0: the image, Lod 0, Prefilter -> down level 0
+    hipLaunchKernelGGL(k_bloom_down0, grid(w0, h0), dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, image, slot), W, H, lvl(s.down, 0), w0, h0, b->MaxColor, b->Threshold);
+    // down pass l: down level l - 1 -> down level l; Lod = l - 1, so the pass that writes level 1 prefilters again (compute.glsl:41, Bloom.cs:85)
+    for (int l = 1; l < levels; l++)
+        hipLaunchKernelGGL((k_bloom_pass<0>), grid(dim(w0, l), dim(h0, l)), dim3(256), 0, ctx->stream, (const uint2*)lvl(s.down, l - 1), (const uint2*)nullptr, dim(w0, l - 1), dim(h0, l - 1), lvl(s.down, l), dim(w0, l), dim(h0, l), l == 1 ? 1 : 0, b->MaxColor, b->Threshold);
+    // up passes: up level l from Upsample(level l + 1 of the up chain — of the DOWN chain in the first pass, Bloom.cs:98) + down level l + 1 (Lod = l + 1 for both samplers)
+    for (int l = levels - 2; l >= 0; l--) {
+        const uint2* a = l == levels - 2 ? lvl(s.down, l + 1) : lvl(s.up, l + 1);
+        hipLaunchKernelGGL((k_bloom_pass<1>), grid(dim(w0, l), dim(h0, l)), dim3(256), 0, ctx->stream, a, (const uint2*)lvl(s.down, l + 1), dim(w0, l + 1), dim(h0, l + 1), lvl(s.up, l), dim(w0, l), dim(h0, l), 0, 0.0f, 0.0f);
+    }
+    hipLaunchKernelGGL(k_bloom_expand, dim3((unsigned)(((size_t)W * H + 255) / 256)), dim3(256), 0, ctx->stream, (const uint2*)lvl(s.up, 0), w0, h0, (float4*)s.out.p, W, H);
+    HIPC(hipGetLastError());
+    s.levels = levels; s.w0 = w0; s.h0 = h0; s.valid = true;
+    return IDKPT_OK;
+}
+// the last bloom of a slot; INVALID_OPERATION when the slot was not bloomed since the last resize
+static int32_t bloom_of(dev_ctx* ctx, const char* who, int32_t slot, BloomSlot** out)
+{
+    REQUIRE(slot >= -1 && slot < ctx->ringSize, std::string(who) + ": slot outside the frame ring (-1: the current slot)");
+    if (slot < 0) slot = ctx->curSlot;
+    if ((size_t)slot >= ctx->bloom.size() || !ctx->bloom[slot].valid) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, std::string(who) + ": the slot was not bloomed since the last resize (idkptBloom)");
+    *out = &ctx->bloom[slot];
+    return IDKPT_OK;
+}
+static int32_t dev_GetBloomInfo(dev_ctx* ctx, int32_t slot, int32_t* levels, int32_t* w0, int32_t* h0)
+{
+    if (!ctx) return IDKPT_ERR_INVALID_ARGUMENT;
+    BloomSlot* s = nullptr;
+    { int rc = bloom_of(ctx, "idkptGetBloomInfo", slot, &s); if (rc) return rc; }
+    if (levels) *levels = s->levels;
+    if (w0) *w0 = s->w0;
+    if (h0) *h0 = s->h0;
+    return IDKPT_OK;
+}
+static int32_t dev_DownloadBloom(dev_ctx* ctx, int32_t slot, int32_t chain, int32_t level, void* dst, size_t bytes)
+{
+    if (!ctx || !dst) return IDKPT_ERR_INVALID_ARGUMENT;
+    REQUIRE(chain == 0 || chain == 1, "idkptDownloadBloom: chain must be 0 (down) or 1 (up)");
+    BloomSlot* s = nullptr;
+    { int rc = bloom_of(ctx, "idkptDownloadBloom", slot, &s); if (rc) return rc; }
+    REQUIRE(level >= 0 && level < s->levels - chain, "idkptDownloadBloom: level outside the chain (the down chain has `levels` levels, the up chain one fewer)");
+    const size_t need = bloom_level_texels(s->w0, s->h0, level) * 8;
+    REQUIRE(bytes == need, "idkptDownloadBloom: bytes must equal the level's width*height*8");
+    HIPC(hipSetDevice(ctx->device));
+    FLUSH_KEEP();
+    HIPC(hipMemcpyAsync(dst, (const char*)(chain ? s->up.p : s->down.p) + bloom_level_offset(s->w0, s->h0, level) * 8, need, hipMemcpyDeviceToHost, ctx->stream));
+    SYNC_CHECKED();
+    return IDKPT_OK;
+}
+static int32_t dev_GetBloomDevicePtr(dev_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes)
+{
+    if (!ctx || !outPtr) return IDKPT_ERR_INVALID_ARGUMENT;
+    BloomSlot* s = nullptr;
+    { int rc = bloom_of(ctx, "idkptGetBloomDevicePtr", slot, &s); if (rc) return rc; }
+    *outPtr = s->out.p;
+    if (outBytes) *outBytes = s->outBytes;
+    return IDKPT_OK;
+}

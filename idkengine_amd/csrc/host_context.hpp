@@ -10,6 +10,13 @@ struct DevBuf {
     template <class T> T* as() const { return (T*)p; }
 };
 
+// idkptBloom (host_bloom.hpp): the buffers of one ring slot — RGBA16F levels of the down and the up chain, the expanded RGBA32F image — and what the last bloom made of them
+struct BloomSlot {
+    DevBuf down, up, out; size_t downBytes = 0, upBytes = 0, outBytes = 0;   // (bytes in front of each buffer's guard)
+    int levels = 0, w0 = 0, h0 = 0; bool valid = false;                      // valid: bloomed since the last resize
+    void release() { down.release(); up.release(); out.release(); downBytes = upBytes = outBytes = 0; valid = false; }
+};
+
 // Tuning / test options (idkptSetDeveloperOption; none is part of the reference's interface and results are bit-identical under all of them:
 // tests/test_gpu_worklist.py, test_gpu_layout.py).  The library itself never reads the environment; the Python host mirror forwards IDKPT_<NAME>.
 struct DevOptions {
@@ -156,6 +163,7 @@ struct dev_ctx {
     DevBuf trRec, contFlag, blockSums, rayO, rayT, rayR, aovA, aovN, hit, hitCost, primHit, queue[2], keys[2], keysTmp, sortKeys, sortVals, contMask, waveCounts, counts, work, sortHist, counters64;
     DevBuf img[3];
     std::vector<DevBuf> disp; std::vector<int> dispFmt;   // idkptPresent: the display image of every ring slot (allocated at the first present of the slot) and its format (enum idkpt_display_format; -1: not presented since the last resize)
+    std::vector<BloomSlot> bloom;   // idkptBloom: per ring slot, allocated at the slot's first bloom
     DevBuf camTab;                                       // per-sample cameras of the batch being launched (ring mode)
     int rowLimit = 0x7fffffff;                           // idkptSetRowRange: at most this many local rows
     idkpt_bounce_exchange_fn exchangeFn = nullptr; void* exchangeUser = nullptr;   // exact multi-GPU deep paths (idkptSetBounceExchange)

@@ -31,6 +31,8 @@ static int alloc_frame_impl(dev_ctx* ctx)
     ctx->accum.assign(ctx->ringSize, 0u); ctx->curSlot = 0; ctx->ringStarted = false;
     for (DevBuf& b : ctx->disp) b.release();                       // display images (idkptPresent) belong to a frame size and a ring: re-made at their next use
     ctx->disp.clear(); ctx->dispFmt.clear();
+    for (BloomSlot& s : ctx->bloom) s.release();                   // ... and so do the bloom chains (idkptBloom)
+    ctx->bloom.clear();
     return IDKPT_OK;
 }
 
@@ -44,8 +46,9 @@ static int alloc_frame_keep_images(dev_ctx* ctx)
     DevBuf saved[3];
     for (int i = 0; i < 3; i++) { saved[i] = ctx->img[i]; ctx->img[i] = DevBuf(); }
     std::vector<DevBuf> disp; std::vector<int> dispFmt; disp.swap(ctx->disp); dispFmt.swap(ctx->dispFmt);   // (the display images stay as well: same size, same ring)
+    std::vector<BloomSlot> bloom; bloom.swap(ctx->bloom);                                                   // (and the bloom chains)
     int rc = alloc_frame(ctx);
-    ctx->disp.swap(disp); ctx->dispFmt.swap(dispFmt);
+    ctx->disp.swap(disp); ctx->dispFmt.swap(dispFmt); ctx->bloom.swap(bloom);
     // The restore is ordered on the context's stream, behind the zero-fill alloc_frame_impl queued there: the stream is non-blocking, so
     // a null-stream copy would be unordered against that fill (the fill could land after the restore and wipe the accumulation).
     hipError_t e = hipSuccess;

@@ -130,6 +130,7 @@ static int32_t dev_Destroy(dev_ctx* ctx)
     for (DevBuf* b : all) b->release();
     for (auto& t : ctx->texData) t.release();
     for (DevBuf& b : ctx->disp) b.release();
+    for (BloomSlot& s : ctx->bloom) s.release();
     builder_scratch_free(ctx);
     if (ctx->hCounts) (void)hipHostFree(ctx->hCounts);
     if (ctx->hOverflow) (void)hipHostFree(ctx->hOverflow);

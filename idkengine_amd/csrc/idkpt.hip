@@ -34,6 +34,7 @@ using namespace ptd;
 #include "kernels_texture.hpp"
 #include "kernels_sky.hpp"
 #include "kernels_present.hpp"
+#include "kernels_bloom.hpp"
 #include "bvh_gpu.hpp"
 #include "bvh_gpu_full.hpp"
 
@@ -47,6 +48,7 @@ using namespace ptd;
 #include "host_queries.hpp"
 #include "host_schedule.hpp"
 #include "host_readback.hpp"
+#include "host_bloom.hpp"
 #include "host_options.hpp"
 #include "transport_rccl.hpp"
 

@@ -822,6 +822,13 @@ int32_t idkptGetDisplayDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size
     return group_gather_rows(c, srcs, texel, c->fullDisp, outPtr, outBytes);
 }
 
+// ---- bloom (host_bloom.hpp): one device, the whole frame — a global filter; a shard of the rows would need halos as wide as the chain
+#define BLOOM_ONE(who, call) do { if (!c) return IDKPT_ERR_INVALID_ARGUMENT; ONE(call); return gfail(c, IDKPT_ERR_INVALID_OPERATION, who ": bloom runs on one device with the whole frame; a multi-device context has none"); } while (0)
+int32_t idkptBloom(idkpt_ctx* c, int32_t slot, int32_t image, const idkpt_bloom* bloom) { BLOOM_ONE("idkptBloom", dev_Bloom(m, slot, image, bloom)); }
+int32_t idkptGetBloomInfo(idkpt_ctx* c, int32_t slot, int32_t* levels, int32_t* w0, int32_t* h0) { BLOOM_ONE("idkptGetBloomInfo", dev_GetBloomInfo(m, slot, levels, w0, h0)); }
+int32_t idkptDownloadBloom(idkpt_ctx* c, int32_t slot, int32_t chain, int32_t level, void* dst, size_t bytes) { BLOOM_ONE("idkptDownloadBloom", dev_DownloadBloom(m, slot, chain, level, dst, bytes)); }
+int32_t idkptGetBloomDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size_t* outBytes) { BLOOM_ONE("idkptGetBloomDevicePtr", dev_GetBloomDevicePtr(m, slot, outPtr, outBytes)); }
+
 int32_t idkptResetAccumulation(idkpt_ctx* c) { if (!c) return IDKPT_ERR_INVALID_ARGUMENT; for (dev_ctx* m : c->dev) dev_ResetAccumulation(m); return IDKPT_OK; }
 int32_t idkptSetSampleSequence(idkpt_ctx* c, uint32_t first, uint32_t stride) { REPLICATE(SetSampleSequence, first, stride); }
 int32_t idkptGetAccumulatedSamples(idkpt_ctx* c, uint32_t* out) { if (!c || !out) return IDKPT_ERR_INVALID_ARGUMENT; return dev_GetAccumulatedSamples(c->dev[0], out); }

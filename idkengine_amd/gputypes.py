@@ -178,6 +178,14 @@ class TonemapSettings(C.Structure):
 IDKPT_DISPLAY_RGBA8, IDKPT_DISPLAY_RGBA32F = 0, 1
 
 
+class BloomSettings(C.Structure):
+    """idkpt_bloom = Bloom.GpuSettings (Source/Render/Bloom.cs:10-18) + MinusLods (Bloom.cs:46); the defaults are the reference's."""
+    _fields_ = [("Threshold", C.c_float), ("MaxColor", C.c_float), ("MinusLods", C.c_int32)]
+
+    def __init__(self, Threshold=1.5, MaxColor=3.8, MinusLods=3):
+        super().__init__(float(Threshold), float(MaxColor), int(MinusLods))
+
+
 class Stats(C.Structure):
     _fields_ = [("RaysTraced", C.c_uint64), ("PrimaryRays", C.c_uint64), ("Frames", C.c_uint64),
                 ("LastAliveCounts", C.c_uint32 * 16), ("LastTraceMs", C.c_float), ("LastFrameMs", C.c_float),

@@ -416,7 +416,7 @@ class PathTracer:
         return out
 
     # ---- display output (idkptPresent / idkptDownloadDisplay / idkptGetDisplayDevicePtr): TonemapAndGammaCorrect.Compute on the device
-    def _present(self, settings, image, slot, fmt):
+    def _present(self, settings, image, slot, fmt, bloom=None):
         formats = {"rgba8": T.IDKPT_DISPLAY_RGBA8, "rgba32f": T.IDKPT_DISPLAY_RGBA32F}
         if fmt not in formats:
             raise ValueError(f"Present: fmt must be 'rgba8' or 'rgba32f', got {fmt!r}")
@@ -425,24 +425,83 @@ class PathTracer:
         if not isinstance(settings, T.TonemapSettings):
             raise TypeError("Present: settings must be a gputypes.TonemapSettings")
         slot = -1 if slot is None else int(slot)
-        self._check(self._L.idkptPresent(self._ctx, slot, int(image), C.addressof(settings), formats[fmt], None, None))
+        add0 = None
+        if bloom is not None:                        # Application.cs:217-223: Bloom.Compute(Result), then TonemapAndGamma.Compute(Result, Bloom.Result)
+            add0, _ = self.bloom_device_ptr(None if bloom is True else bloom, image, slot)
+        self._check(self._L.idkptPresent(self._ctx, slot, int(image), C.addressof(settings), formats[fmt], add0, None))
         return slot, formats[fmt]
 
-    def Present(self, settings=None, image=0, slot=None, fmt="rgba8"):
+    def Present(self, settings=None, image=0, slot=None, fmt="rgba8", bloom=None):
         """TonemapAndGamma.Compute(PathTracer.Result) + the download of its R8G8B8A8Unorm result: the tone-mapped, sRGB-encoded, dithered image of `image` (0-2) of ring
         slot `slot` (None: the current one) as an (H, W, 4) numpy array — uint8 for fmt "rgba8", float32 (the value before quantisation) for "rgba32f".  settings: a
-        gputypes.TonemapSettings; None = the reference's defaults with DoTonemapAndSrgbTransform = not DoDebugBVHTraversal, as Application.cs:222 sets it."""
-        slot, f = self._present(settings, image, slot, fmt)
+        gputypes.TonemapSettings; None = the reference's defaults with DoTonemapAndSrgbTransform = not DoDebugBVHTraversal, as Application.cs:222 sets it.
+        bloom: None = no bloom (an unbound Sampler1); a gputypes.BloomSettings (or True: the reference's defaults) runs idkptBloom on the same image first and adds its
+        expanded image as the shader's Sampler1, all on the device (one device, whole frame only)."""
+        slot, f = self._present(settings, image, slot, fmt, bloom)
         out = np.zeros((self.rows, self.width, 4), np.float32 if f == T.IDKPT_DISPLAY_RGBA32F else np.uint8)
         self._check(self._L.idkptDownloadDisplay(self._ctx, slot, out.ctypes.data, out.nbytes))
         return out
 
-    def present_device_ptr(self, settings=None, image=0, slot=None, fmt="rgba8"):
-        """idkptPresent + idkptGetDisplayDevicePtr: (device pointer, bytes) of the display image, valid in stream order; nothing is downloaded or waited for."""
-        slot, _ = self._present(settings, image, slot, fmt)
+    def present_device_ptr(self, settings=None, image=0, slot=None, fmt="rgba8", bloom=None):
+        """idkptPresent + idkptGetDisplayDevicePtr: (device pointer, bytes) of the display image, valid in stream order; nothing is downloaded or waited for.  bloom: as Present."""
+        slot, _ = self._present(settings, image, slot, fmt, bloom)
         p = C.c_void_p(); n = C.c_size_t()
         self._check(self._L.idkptGetDisplayDevicePtr(self._ctx, slot, C.byref(p), C.byref(n)))
         return p.value, n.value
+
+    # ---- bloom (idkptBloom / idkptGetBloomInfo / idkptDownloadBloom / idkptGetBloomDevicePtr): Bloom.Compute on the device
+    def bloom_device_ptr(self, settings=None, image=0, slot=None):
+        """idkptBloom + idkptGetBloomDevicePtr: (device pointer, bytes) of the expanded RGBA32F image — idkptPresent's dAdd0 —, valid in stream order; nothing is waited for."""
+        if settings is None:
+            settings = T.BloomSettings()
+        if not isinstance(settings, T.BloomSettings):
+            raise TypeError("Bloom: settings must be a gputypes.BloomSettings")
+        slot = -1 if slot is None else int(slot)
+        self._check(self._L.idkptBloom(self._ctx, slot, int(image), C.addressof(settings)))
+        p = C.c_void_p(); n = C.c_size_t()
+        self._check(self._L.idkptGetBloomDevicePtr(self._ctx, slot, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def Bloom(self, settings=None, image=0, slot=None):
+        """Bloom.Compute(image `image` (0-2) of ring slot `slot`; None: the current one) and what the tonemap shader reads of its result: the up chain's level 0 magnified to
+        the frame, an (H, W, 4) float32 array (rgb, 1.0).  settings: a gputypes.BloomSettings; None = the reference's defaults (1.5, 3.8, MinusLods 3)."""
+        p, n = self.bloom_device_ptr(settings, image, slot)
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        if n != out.nbytes:
+            raise IdkPtError(f"Bloom: the expanded image has {n} bytes, expected {out.nbytes} (height * width * 16)")
+        self.read_device(p, out)
+        return out
+
+    def read_device(self, ptr, out):
+        """Copies out.nbytes bytes at device pointer `ptr` (one the library returned for this context: image_device_ptr, present_device_ptr, bloom_device_ptr ...) into the
+        C-contiguous numpy array `out`, ordered on the context's stream (idkptGetStream) behind what the library launched there; waits for the copy and returns `out`."""
+        import torch                                   # (the plumbing: PyTorch-ROCm carries the copy; the stream is the library's)
+        if not isinstance(out, np.ndarray) or not out.flags["C_CONTIGUOUS"]:
+            raise ValueError("read_device: out must be a C-contiguous numpy array")
+        st = C.c_void_p(); self._check(self._L.idkptGetStream(self._ctx, C.byref(st)))
+        stream = torch.cuda.ExternalStream(st.value)
+        holder = type("DevArray", (), {"__cuda_array_interface__": {"shape": (int(out.nbytes),), "typestr": "|u1", "data": (int(ptr), False), "version": 2}})()
+        with torch.cuda.stream(stream):
+            host = torch.as_tensor(holder, device="cuda").to("cpu")
+        stream.synchronize()
+        self._check(self._L.idkptSynchronize(self._ctx))   # (reports what the frame's kernels reported: a traversal stack overflow)
+        out.view(np.uint8).reshape(-1)[:] = host.numpy()
+        return out
+
+    def bloom_info(self, slot=None):
+        """idkptGetBloomInfo of the slot's last bloom: (levels, w0, h0)"""
+        lv, w0, h0 = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(self._L.idkptGetBloomInfo(self._ctx, -1 if slot is None else int(slot), C.byref(lv), C.byref(w0), C.byref(h0)))
+        return lv.value, w0.value, h0.value
+
+    def bloom_level(self, chain, level, slot=None):
+        """idkptDownloadBloom: level `level` of the down (chain 0) or up (chain 1) chain of the slot's last bloom, an (h, w, 4) float16 array (the stored RGBA16F bits)."""
+        levels, w0, h0 = self.bloom_info(slot)
+        if chain not in (0, 1) or not 0 <= int(level) < levels - chain:
+            raise ValueError(f"bloom_level: chain {chain!r} level {level!r} outside the chains ({levels} down levels, {levels - 1} up levels)")
+        out = np.zeros((max(h0 >> int(level), 1), max(w0 >> int(level), 1), 4), np.float16)
+        self._check(self._L.idkptDownloadBloom(self._ctx, -1 if slot is None else int(slot), int(chain), int(level), out.ctypes.data, out.nbytes))
+        return out
 
     def enable_counters(self, on=True):
         self._check(self._L.idkptEnableCounters(self._ctx, 1 if on else 0))

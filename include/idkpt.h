@@ -196,10 +196,11 @@ typedef struct idkpt_stats {
     uint32_t InstUnifiedTopDepth;  /* depth of that top */
 } idkpt_stats;
 /* The layout above only ever GROWS at its end, and IDKPT_ABI_VERSION counts the growths (and every other change a host compiled against an older header could trip over: new
- * enum values of idkpt_buffer or idkpt_texture_format, new fields of idkpt_texture, new entry points: 5 = idkptComputeSky / idkptUpdateSky / idkptDownloadSky, 6 = idkptPresent / idkptDownloadDisplay / idkptGetDisplayDevicePtr).  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
+ * enum values of idkpt_buffer or idkpt_texture_format, new fields of idkpt_texture, new entry points: 5 = idkptComputeSky / idkptUpdateSky / idkptDownloadSky, 6 = idkptPresent / idkptDownloadDisplay / idkptGetDisplayDevicePtr,
+ * 7 = idkptBloom / idkptGetBloomInfo / idkptDownloadBloom / idkptGetBloomDevicePtr).  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
  * of ITS struct to idkptGetStatsSized and gets exactly that many bytes; idkptGetStats(ctx, out) is idkptGetStatsSized(ctx, out, sizeof(idkpt_stats)) of the header the LIBRARY
  * was built with — for hosts built from the same tree.  idkptGetAbiVersion() lets a host refuse a library older than the header it was written against. */
-#define IDKPT_ABI_VERSION 6
+#define IDKPT_ABI_VERSION 7
 
 /* ---- lifetime --------------------------------------------------------------------------- */
 /* new PathTracer(w,h,settings) (PathTracer.cs:170-212).  deviceCount = 1: the reference's situation, one GPU.
@@ -434,8 +435,8 @@ IDKPT_API int32_t idkptGetFrameDevicePtr(idkpt_ctx* ctx, int32_t slot, int32_t i
 
 /* ---- display output (ABI 6): TonemapAndGammaCorrect.Compute (Source/Render/TonemapAndGammaCorrecter.cs, Shaders/TonemapAndGammaCorrect/compute.glsl) -------------------
  * The one pass between PathTracer.Result and the swapchain (Source/Application.cs:217-223): AgX tonemap, sRGB transfer and the 8 x 8 Bayer dither, run on the device so
- * that a displayed frame leaves it as 4 bytes per pixel instead of 16.  Bloom (the shader's Sampler1 / Sampler2 come from the host) and resampling to another
- * presentation size stay with the host: the display image has the render size. */
+ * that a displayed frame leaves it as 4 bytes per pixel instead of 16.  The shader's Sampler1 / Sampler2 are device pointers (dAdd0 / dAdd1): idkptBloom below fills
+ * Sampler1 as the engine does.  Resampling to another presentation size stays with the host: the display image has the render size. */
 typedef struct idkpt_tonemap { float Exposure, Saturation, Linear, Peak, Compression; int32_t DoTonemapAndSrgbTransform; } idkpt_tonemap;
 /* TonemapAndGammaCorrect.GpuSettings, same order; the reference's defaults 0.45, 1.06, 0.18, 1.0, 0.1, 1.  DoTonemapAndSrgbTransform = 0 is the reference's
  * DoDebugBVHTraversal path (Application.cs:222): clamp to [0, 1], no sRGB, dither. */
@@ -460,6 +461,39 @@ IDKPT_API int32_t idkptPresent(idkpt_ctx* ctx, int32_t slot, int32_t image, cons
  * idkptGetFrameDevicePtr does (RCCL or peer copies), 4 bytes per pixel for RGBA8. */
 IDKPT_API int32_t idkptDownloadDisplay(idkpt_ctx* ctx, int32_t slot, void* dst, size_t bytes);
 IDKPT_API int32_t idkptGetDisplayDevicePtr(idkpt_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes);
+
+/* ---- bloom (ABI 7): Bloom.Compute (Source/Render/Bloom.cs:56-147, Shaders/Bloom/compute.glsl) --------------------------------------------------------------------------
+ * The pass Application.cs:217-223 runs between PathTracer.Result and TonemapAndGamma.Compute (IsBloom is on by default): a mip chain of the image is filtered down
+ * (13 taps) and up again (9 taps + the down level), and the tonemap shader adds the result as its Sampler1.  Prefilter (clamp to MaxColor, soft threshold with a knee
+ * of 0.2) runs TWICE, in the pass that writes down level 0 and again in the pass that writes down level 1: the shader prefilters `if (Lod == 0)`, and Bloom.cs:85
+ * uploads Lod = currentWriteLod - 1, which is 0 for both.  That is what the reference computes, and what a host comparing against its own bloom must expect.
+ * Sizes: w0 = width / 2, h0 = height / 2 (integer division); levels = max(ilogb(max(w0, h0)) + 1 - MinusLods, 2); level l is max(w0 >> l, 1) x max(h0 >> l, 1); the
+ * down chain has `levels` levels, the up chain `levels - 1`.  The up pass that writes up level l reads level l + 1 of the up chain — of the DOWN chain in the first
+ * pass — and adds down level l + 1, as the reference does.
+ * Arithmetic: the shader's, operation for operation in binary32 (csrc/bloom_texel.hpp): textureLod / textureLodOffset are a linear filter with clamp to edge at an
+ * explicit level, uv = (texel + 0.5) / size of the written level, f = u * size - 0.5 + offset, floor, fractional weights, clamped indices, mix(x, y, a) = x (1 - a) + y a.
+ * Storage (the contract): levels are R16G16B16A16Float like the reference's, 8 bytes per texel in memory order R, G, B, A with alpha 1.0 (0x3C00).  float -> half ROUNDS
+ * TOWARD ZERO; a finite value beyond 65504 is stored as 65504; subnormal halves are produced; +-Inf stays, NaN becomes a quiet NaN.  (Mesa llvmpipe stores every
+ * texel of the test fixture by this rule.)
+ * The expanded image: what the tonemap shader reads, texture(Sampler1, (pixel + 0.5) / size) — up level 0 magnified bilinearly (linear, clamp to edge) — for every pixel
+ * of the frame as RGBA32F (rgb, 1.0).  idkptGetBloomDevicePtr returns it; passed as idkptPresent's dAdd0 it gives the engine's default displayed frame with nothing
+ * computed on the host.
+ * Scope: ONE device and the WHOLE frame.  Bloom is a global filter (the last level mixes the whole image); a shard of the rows would need halos as wide as the chain.
+ * A multi-device context, and a context that holds row bands or a strip (idkptSetRowSharding / idkptSetRowBands / idkptSetRowRange), get IDKPT_ERR_INVALID_OPERATION.
+ * Like idkptPresent: queued samples are launched first, the call does not wait for the GPU (one launch per pass, 2 * levels launches, on the context's stream); buffers
+ * belong to a ring slot (the down chain, the up chain, the expanded image), are allocated at the slot's first bloom, re-made by idkptSetSize / idkptSetFrameRing and the
+ * row layout calls, kept by idkptSetMaxBatch, and each ends with 64 guard bytes of value 0xA5 that nothing writes; a context that never blooms allocates nothing.
+ * Validated before anything is launched: slot (-1: the current slot) and image in range, Threshold and MaxColor finite, MinusLods >= 0 (IDKPT_ERR_INVALID_ARGUMENT);
+ * no size set, width < 2 or height < 2, a shard of the rows (IDKPT_ERR_INVALID_OPERATION). */
+typedef struct idkpt_bloom { float Threshold, MaxColor; int32_t MinusLods; } idkpt_bloom;   /* Bloom.GpuSettings + MinusLods; the reference's defaults 1.5, 3.8, 3 */
+IDKPT_API int32_t idkptBloom(idkpt_ctx* ctx, int32_t slot, int32_t image, const idkpt_bloom* bloom);   /* Bloom.Compute(image `image` of slot `slot`) */
+/* The last bloom of a slot (-1: the current slot); IDKPT_ERR_INVALID_OPERATION if the slot was not bloomed since the last resize.  Out pointers may be NULL.
+ * idkptDownloadBloom copies the RGBA16F bits of one level (chain 0 = down, 1 = up; `bytes` must equal the level's width * height * 8; chain, level or bytes wrong:
+ * IDKPT_ERR_INVALID_ARGUMENT) and synchronises like the other Download calls.  idkptGetBloomDevicePtr returns the expanded image (height * width * 16 bytes) and does
+ * not wait: the pointer is valid in stream order (idkptGetStream) until the next bloom of that slot or resize. */
+IDKPT_API int32_t idkptGetBloomInfo(idkpt_ctx* ctx, int32_t slot, int32_t* levels, int32_t* w0, int32_t* h0);
+IDKPT_API int32_t idkptDownloadBloom(idkpt_ctx* ctx, int32_t slot, int32_t chain, int32_t level, void* dst, size_t bytes);
+IDKPT_API int32_t idkptGetBloomDevicePtr(idkpt_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes);
 
 /* ---- render ----------------------------------------------------------------------------- */
 /* PathTracer.ResetAccumulation (PathTracer.cs:334-337) */
