@@ -711,6 +711,54 @@ static int32_t dev_UpdateSky(dev_ctx* ctx, int32_t faceSize, int32_t format, con
     return IDKPT_OK;
 }
 
+// idkptUnprojectSky (kernels_unproject.hpp): everything is decided here, before anything resident changes.  *outS: the face size the call produces.  scan: read every
+// texel for Inf / NaN (the one expensive part: a multi-device context does it once, in front of the group's flush, and not again on member 0).
+static int32_t sky_validate_unproject(dev_ctx* ctx, int32_t width, int32_t height, int32_t channels, const float* pixels, int32_t faceSize, bool scan, int32_t* outS)
+{
+    if (!ctx->haveScene) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptUnprojectSky: no scene uploaded");
+    REQUIRE(pixels != nullptr, "idkptUnprojectSky: null pixels");
+    REQUIRE(width >= 1 && width <= 16384 && height >= 1 && height <= 8192, "idkptUnprojectSky: width must be in 1..16384 and height in 1..8192");
+    REQUIRE(channels == 3 || channels == 4, "idkptUnprojectSky: channels must be 3 or 4");
+    REQUIRE(faceSize >= 0 && faceSize <= 4096, "idkptUnprojectSky: faceSize must be in 0..4096 (0: width / 4)");
+    REQUIRE(faceSize != 0 || width >= 4, "idkptUnprojectSky: faceSize 0 means width / 4, which needs width >= 4");
+    const int32_t S = faceSize ? faceSize : width / 4;                  // SkyBoxManager.cs:124 (<= 4096 as width <= 16384)
+    if (scan) {
+        const uint32_t* w = reinterpret_cast<const uint32_t*>(pixels); uint32_t bad = 0;
+        for (size_t k = 0, e = (size_t)width * height * channels; k < e; k++) bad |= (uint32_t)((w[k] & 0x7f800000u) == 0x7f800000u);
+        REQUIRE(!bad, "idkptUnprojectSky: every texel must be finite");
+    }
+    *outS = S;
+    return IDKPT_OK;
+}
+// Staging follows idkptUpdateTexture: the host's floats go to texStage (free here: see dev_UpdateSky; an 8-bit idkptUpdateSky that is still expanding from it is ahead of
+// this call's copy on the stream, and the stream is drained before the buffer is reallocated), the packed RGBA16F panorama sits behind them at a 256-byte boundary, and
+// the call ends with the stream idle — `pixels` is borrowed for the call only and the staging is free again.  The staging buffer — the one large allocation of the call —
+// is made BEFORE sky_begin, which may release a smaller resident sky: when it cannot be had, the call fails with the old sky untouched.  Peak device memory on top of the resident faces: channels * 4 + 8 bytes per source texel; a staging buffer that grew beyond
+// UNPROJECT_KEEP_BYTES is released before the call returns, a smaller one is kept for the next texture or sky.
+#define UNPROJECT_KEEP_BYTES ((size_t)64 << 20)
+static int32_t dev_UnprojectSky(dev_ctx* ctx, int32_t width, int32_t height, int32_t channels, const float* pixels, int32_t faceSize, bool scanned = false)
+{
+    if (!ctx) return IDKPT_ERR_INVALID_ARGUMENT;
+    int32_t S = 0;
+    { int rc = sky_validate_unproject(ctx, width, height, channels, pixels, faceSize, !scanned, &S); if (rc) return rc; }
+    const size_t texels = (size_t)width * height, srcBytes = texels * channels * 4, packOff = (srcBytes + 255) & ~(size_t)255, total = packOff + texels * 8;
+    HIPC(hipSetDevice(ctx->device));
+    if (!ctx->texStage.p || ctx->texStage.bytes < total) { HIPC(hipStreamSynchronize(ctx->stream)); HIPC(ctx->texStage.ensure(total)); }
+    { int rc = sky_begin(ctx, S); if (rc) return rc; }
+    HIPC(hipMemcpyAsync(ctx->texStage.p, pixels, srcBytes, hipMemcpyHostToDevice, ctx->stream));
+    uint2* packed = (uint2*)((char*)ctx->texStage.p + packOff);
+    if (channels == 4) hipLaunchKernelGGL(k_equirect_pack<4>, dim3((unsigned)((texels + 255) / 256)), dim3(256), 0, ctx->stream, (const float*)ctx->texStage.p, packed, (uint32_t)texels);
+    else hipLaunchKernelGGL(k_equirect_pack<3>, dim3((unsigned)(((texels + 3) / 4 + 255) / 256)), dim3(256), 0, ctx->stream, (const float*)ctx->texStage.p, packed, (uint32_t)texels);
+    HIPC(hipGetLastError());
+    const uint32_t cube = 6u * (uint32_t)S * (uint32_t)S;
+    hipLaunchKernelGGL(k_sky_unproject, dim3((cube + 255u) / 256u), dim3(256), 0, ctx->stream, (const uint2*)packed, (int)width, (int)height, ctx->sky.as<float4>(), (int)S);
+    HIPC(hipGetLastError());
+    ctx->skySize = S;
+    HIPC(hipStreamSynchronize(ctx->stream));
+    if (ctx->texStage.bytes > UNPROJECT_KEEP_BYTES) ctx->texStage.release();
+    return IDKPT_OK;
+}
+
 // multi-device contexts (idkpt_api.hpp idkptUpdateSky): this member adopts the sky member `src` uploaded.  copy: device to device like the scene buffers (member_copy), ordered
 // behind src->evSky — recorded on the source's stream after its upload (sky_mark) — and marked in turn, so that the source can wait for this read before it writes its sky
 // again; !copy: only the room is made (the caller moves the bytes: one RCCL broadcast over all members' streams, which orders itself).

@@ -33,6 +33,7 @@ using namespace ptd;
 #include "kernels_scene.hpp"
 #include "kernels_texture.hpp"
 #include "kernels_sky.hpp"
+#include "kernels_unproject.hpp"
 #include "kernels_present.hpp"
 #include "kernels_bloom.hpp"
 #include "bvh_gpu.hpp"

@@ -696,16 +696,10 @@ int32_t idkptComputeSky(idkpt_ctx* c, int32_t faceSize, const idkpt_atmosphere* 
     ALL(dev_ComputeSky(m, faceSize, atmosphere));       // (validates; nothing is changed when it fails on the first member)
     return IDKPT_OK;
 }
-// the faces cross PCIe once, to member 0 (expanded there when they are 8-bit), and reach the other members the way the scene does: one RCCL broadcast, or peer copies
-int32_t idkptUpdateSky(idkpt_ctx* c, int32_t faceSize, int32_t format, const void* faces)
+// member 0's resident sky reaches the other members the way the scene does: one RCCL broadcast, or peer copies
+static int group_sky_replicate(idkpt_ctx* c)
 {
-    if (!c) return IDKPT_ERR_INVALID_ARGUMENT;
-    ONE(dev_UpdateSky(m, faceSize, format, faces));
     dev_ctx* m0 = c->dev[0];
-    { int rc = sky_validate_update(m0, faceSize, format, faces); if (rc) return mfail(c, m0, rc); }
-    GFLUSH();
-    { int rc = group_sky_writable(c); if (rc) return rc; }
-    { int rc = dev_UpdateSky(m0, faceSize, format, faces); if (rc) return mfail(c, m0, rc); }
     { int rc = sky_mark(m0); if (rc) return mfail(c, m0, rc); }
     const size_t n = c->n(), bytes = (size_t)6 * m0->skySize * m0->skySize * 16;
     bool moved = false;
@@ -719,6 +713,30 @@ int32_t idkptUpdateSky(idkpt_ctx* c, int32_t faceSize, int32_t format, const voi
     if (!moved) for (size_t d = 1; d < n; d++) { int rc = dev_SkyFrom(c->dev[d], m0, true); if (rc) return mfail(c, c->dev[d], rc); }
     (void)hipSetDevice(m0->device);
     return IDKPT_OK;
+}
+// the faces cross PCIe once, to member 0 (expanded there when they are 8-bit), and reach the other members the way the scene does: one RCCL broadcast, or peer copies
+int32_t idkptUpdateSky(idkpt_ctx* c, int32_t faceSize, int32_t format, const void* faces)
+{
+    if (!c) return IDKPT_ERR_INVALID_ARGUMENT;
+    ONE(dev_UpdateSky(m, faceSize, format, faces));
+    dev_ctx* m0 = c->dev[0];
+    { int rc = sky_validate_update(m0, faceSize, format, faces); if (rc) return mfail(c, m0, rc); }
+    GFLUSH();
+    { int rc = group_sky_writable(c); if (rc) return rc; }
+    { int rc = dev_UpdateSky(m0, faceSize, format, faces); if (rc) return mfail(c, m0, rc); }
+    return group_sky_replicate(c);
+}
+// an equirectangular panorama: member 0 stages and unprojects (the source is as large as the result: shipping it to every member buys nothing), the faces then travel as idkptUpdateSky's do
+int32_t idkptUnprojectSky(idkpt_ctx* c, int32_t width, int32_t height, int32_t channels, const float* pixels, int32_t faceSize)
+{
+    if (!c) return IDKPT_ERR_INVALID_ARGUMENT;
+    ONE(dev_UnprojectSky(m, width, height, channels, pixels, faceSize));
+    dev_ctx* m0 = c->dev[0];
+    { int32_t S = 0; int rc = sky_validate_unproject(m0, width, height, channels, pixels, faceSize, true, &S); if (rc) return mfail(c, m0, rc); }   // (the one scan of the texels)
+    GFLUSH();
+    { int rc = group_sky_writable(c); if (rc) return rc; }
+    { int rc = dev_UnprojectSky(m0, width, height, channels, pixels, faceSize, true); if (rc) return mfail(c, m0, rc); }
+    return group_sky_replicate(c);
 }
 int32_t idkptDownloadSky(idkpt_ctx* c, int32_t* outFaceSize, float* dst, size_t dstBytes)
 {

@@ -406,6 +406,19 @@ class PathTracer:
             raise ValueError("UpdateSky: faces must be C-contiguous (np.ascontiguousarray)")
         self._check(self._L.idkptUpdateSky(self._ctx, int(faces.shape[1]), format, faces.ctypes.data))
 
+    def UnprojectSky(self, image, face_size=None):
+        """idkptUnprojectSky (SkyBoxManager.LoadSkyBoxEquirectangular): `image` is the equirectangular panorama, a C-contiguous (H, W, 3) or (H, W, 4) float32 array, row 0
+        the row GL receives first; face_size None = W // 4, as the reference sizes its cube map.  The faces are unprojected on the device and become the scene's sky; the
+        call synchronises (load time).  A new environment invalidates what was accumulated: the accumulation is reset."""
+        if not isinstance(image, np.ndarray) or image.dtype != np.float32:
+            raise TypeError(f"UnprojectSky: image must be a float32 array, got {getattr(image, 'dtype', type(image).__name__)}")
+        if image.ndim != 3 or image.shape[2] not in (3, 4) or image.shape[0] < 1 or image.shape[1] < 1:
+            raise ValueError(f"UnprojectSky: image must have shape (H, W, 3) or (H, W, 4), got {image.shape}")
+        if not image.flags["C_CONTIGUOUS"]:
+            raise ValueError("UnprojectSky: image must be C-contiguous (np.ascontiguousarray)")
+        self._check(self._L.idkptUnprojectSky(self._ctx, int(image.shape[1]), int(image.shape[0]), int(image.shape[2]), image.ctypes.data, 0 if face_size is None else int(face_size)))
+        self.ResetAccumulation()
+
     def DownloadSky(self):
         """idkptDownloadSky: the resident faces, a (6, S, S, 4) float32 array (S = 0: no sky)."""
         s = C.c_int32()

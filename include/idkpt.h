@@ -197,10 +197,10 @@ typedef struct idkpt_stats {
 } idkpt_stats;
 /* The layout above only ever GROWS at its end, and IDKPT_ABI_VERSION counts the growths (and every other change a host compiled against an older header could trip over: new
  * enum values of idkpt_buffer or idkpt_texture_format, new fields of idkpt_texture, new entry points: 5 = idkptComputeSky / idkptUpdateSky / idkptDownloadSky, 6 = idkptPresent / idkptDownloadDisplay / idkptGetDisplayDevicePtr,
- * 7 = idkptBloom / idkptGetBloomInfo / idkptDownloadBloom / idkptGetBloomDevicePtr).  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
+ * 7 = idkptBloom / idkptGetBloomInfo / idkptDownloadBloom / idkptGetBloomDevicePtr, 8 = idkptUnprojectSky).  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
  * of ITS struct to idkptGetStatsSized and gets exactly that many bytes; idkptGetStats(ctx, out) is idkptGetStatsSized(ctx, out, sizeof(idkpt_stats)) of the header the LIBRARY
  * was built with — for hosts built from the same tree.  idkptGetAbiVersion() lets a host refuse a library older than the header it was written against. */
-#define IDKPT_ABI_VERSION 7
+#define IDKPT_ABI_VERSION 8
 
 /* ---- lifetime --------------------------------------------------------------------------- */
 /* new PathTracer(w,h,settings) (PathTracer.cs:170-212).  deviceCount = 1: the reference's situation, one GPU.
@@ -339,6 +339,22 @@ IDKPT_API int32_t idkptComputeSky(idkpt_ctx* ctx, int32_t faceSize, const idkpt_
  * (6 * S * S texels, face order +X, -X, +Y, -Y, +Z, -Z, rows as SkyFaces); 8-bit texels are expanded on the device exactly as the texture table decodes them (UNORM c / 255;
  * sRGB on R, G, B, alpha linear).  faces == NULL or faceSize == 0: no sky (black).  faceSize 0..4096.  A multi-device context uploads once and replicates device to device. */
 IDKPT_API int32_t idkptUpdateSky(idkpt_ctx* ctx, int32_t faceSize, int32_t format, const void* faces);
+/* SkyBoxManager.LoadSkyBoxEquirectangular (ABI 8; Source/Render/SkyBoxManager.cs:115-146): an equirectangular panorama — what ImageLoader.Load(path, RGB, true) holds of an
+ * .hdr file — is unprojected on the device into the six faces (csrc/kernels_unproject.hpp, csrc/unproject_texel.hpp) and becomes the scene's sky.  pixels: `height` rows of
+ * `width` texels of `channels` floats (3, or 4 with alpha), row 0 the row GL receives first (t = 0); borrowed for the call only.  faceSize 0 = width / 4 (integer division,
+ * as the reference allocates its cube map) or an explicit 1..4096.  The library does what the reference's GL does: the floats are rounded to an R16G16B16A16Float image
+ * (to nearest even, subnormal halves produced; alpha 1.0 for three channels; a finite value whose nearest half would be infinite is stored as +-65504 — the one deliberate
+ * deviation), Shaders/UnprojectEquirectangular/compute.glsl runs per cube texel in binary32 (REPEAT-wrapped linear filter, SrgbToLinear on the HDR data as the reference
+ * applies it) and its result is rounded toward zero to the half the reference's R16G16B16A16Float cube map holds.  The resident form is the usual one, 6 x S x S RGBA32F:
+ * every resident value is exactly representable in binary16.  Alpha is FILTERED like the colours, not set: where the panorama's alpha is 1.0 (three channels) the filter's
+ * (1 - a) + a is 1 or one binary32 ulp below it, and the store truncates the latter to the half below 1 — idkptDownloadSky shows 1.0 or 0.99951171875 (0x3BFF) per texel
+ * (the reference's GL forms the sum otherwise and holds 1.0).  Nothing in the library reads a sky texel's alpha.
+ * INVALID_ARGUMENT: width outside 1..16384 (or < 4 with faceSize 0), height outside 1..8192, channels not 3 or 4, faceSize outside 0..4096, pixels NULL, any texel Inf or
+ * NaN; INVALID_OPERATION: no scene; nothing resident changes in either case.  Ordered like the other two updates (queued samples are launched first, with the old sky), but a
+ * load-time call like idkptUpdateTexture: it SYNCHRONISES — the context's stream is idle when it returns.  Device memory during the call, on top of the faces:
+ * channels * 4 + 8 bytes per source texel (released before the call returns when above 64 MiB).  A multi-device context unprojects on its first member and replicates the
+ * faces device to device. */
+IDKPT_API int32_t idkptUnprojectSky(idkpt_ctx* ctx, int32_t width, int32_t height, int32_t channels, const float* pixels, int32_t faceSize);
 /* the resident faces (always RGBA32F): *outFaceSize = S (0: no sky); dst != NULL receives 6 * S * S * 16 bytes (queued samples are launched first and the call synchronises,
  * like the other Download calls; dstBytes too small: IDKPT_ERR_INVALID_ARGUMENT); dst == NULL only fills outFaceSize.  A multi-device context reads its first member's copy. */
 IDKPT_API int32_t idkptDownloadSky(idkpt_ctx* ctx, int32_t* outFaceSize, float* dst, size_t dstBytes);
