@@ -145,13 +145,26 @@ static int ver_grow(dev_ctx* ctx, int b)
     ctx->valloc[b] = ctx->verSlots;
     return IDKPT_OK;
 }
-// Where an update may write buffer b: *dst = the slot to write, *src = the slot that holds the current state (== *dst when the update can go in place).
-// `full`: the update rewrites every byte of the buffer's state (nothing to carry over).  May launch queued samples / complete a deferred bounce when no slot is free.
-static int ver_writable(dev_ctx* ctx, int b, bool full, char** src, char** dst)
+// what the library derived from buffer b is stale once b is written: re-derived before its next use
+static void ver_invalidate(dev_ctx* ctx, int b)
 {
     if (b == VB_NODES) ctx->pairValid = false;
     if (b == VB_NODES || b == VB_TRIVERTS) { ctx->wideFillValid = false; ctx->imarksValid = false; }   // (node boxes or triangle positions are about to change: boxes and leaf records of the wide nodes, and the triangle marks, are re-derived before their next use)
     if (b == VB_NODES || b == VB_XFORMS) { ctx->itlasValid = false; ctx->instRecValid = false; }    // (root boxes or transforms are about to change: the library's own TLAS is rebuilt before its next use)
+}
+static int ver_writable_slot(dev_ctx* ctx, int b, bool full, char** src, char** dst);
+// Where an update may write buffer b: *dst = the slot to write, *src = the slot that holds the current state (== *dst when the update can go in place).
+// `full`: the update rewrites every byte of the buffer's state (nothing to carry over).  May launch queued samples / complete a deferred bounce when no slot is free.
+// (the invalidation comes AFTER the slot is found: finding it may launch the queued samples, and that launch derives — and marks valid — everything it needs from the state that is
+// about to be overwritten; tests/test_gpu_zy_update_sequences.py test_update_behind_a_queued_sample_invalidates_what_its_launch_derived)
+static int ver_writable(dev_ctx* ctx, int b, bool full, char** src, char** dst)
+{
+    const int rc = ver_writable_slot(ctx, b, full, src, dst);
+    ver_invalidate(ctx, b);
+    return rc;
+}
+static int ver_writable_slot(dev_ctx* ctx, int b, bool full, char** src, char** dst)
+{
     const int p = ctx->vcur[b];
     auto free_slot = [&](uint64_t busy) { if (ctx->verSlots > 1 && ctx->vbytes[b] > 0) for (int k = 0; k < ctx->verSlots; k++) if (!((busy >> k) & 1ull)) return k; return -1; };
     uint64_t pend = 0; for (const PendingSample& ps : ctx->pending) pend |= 1ull << ps.vs[b];
