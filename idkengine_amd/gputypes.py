@@ -262,6 +262,12 @@ class Scene:
 (IDKPT_BUF_MESH_TRANSFORMS, IDKPT_BUF_VERTEX_POSITIONS, IDKPT_BUF_VERTICES, IDKPT_BUF_MESHES, IDKPT_BUF_MATERIALS, IDKPT_BUF_LIGHTS,
  IDKPT_BUF_BLAS_NODES, IDKPT_BUF_TLAS_NODES, IDKPT_BUF_JOINT_MATRICES, IDKPT_BUF_WIDE_NODES, IDKPT_BUF_WIDE_LEAVES, IDKPT_BUF_WIDE_COUNTS) = range(12)
 
+# GpuPerFrameData (include/idkpt_types.h; Source/GpuTypes/GpuPerFrameData.cs:5-21): the path tracer reads InvView, ViewPos and InvProjection
+GpuPerFrameData = np.dtype([("ProjView", "<f4", 16), ("View", "<f4", 16), ("InvView", "<f4", 16), ("PrevView", "<f4", 16), ("ViewPos", "<f4", 3), ("Frame", "<u4"),
+                            ("Projection", "<f4", 16), ("InvProjection", "<f4", 16), ("InvProjView", "<f4", 16), ("PrevProjView", "<f4", 16),
+                            ("NearPlane", "<f4"), ("FarPlane", "<f4"), ("DeltaRenderTime", "<f4"), ("Time", "<f4")])
+assert GpuPerFrameData.itemsize == 544 and GpuPerFrameData.fields["InvView"][1] == 128 and GpuPerFrameData.fields["ViewPos"][1] == 256 and GpuPerFrameData.fields["InvProjection"][1] == 336
+
 
 # ray queries / RT shadows (include/idkpt.h: idkpt_ray, idkpt_hit, idkpt_shadow_params, enum idkpt_trace_flags)
 RayQuery = np.dtype([("Origin", "<f4", 3), ("MaxDist", "<f4"), ("Direction", "<f4", 3), ("_pad0", "<u4")])

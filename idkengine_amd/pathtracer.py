@@ -174,6 +174,13 @@ class PathTracer:
         ip = np.ascontiguousarray(cam.inv_projection, np.float32); iv = np.ascontiguousarray(cam.inv_view, np.float32); vp = np.ascontiguousarray(cam.position, np.float32)
         self._check(self._L.idkptSetPerFrame(self._ctx, ip.ctypes.data, iv.ctypes.data, vp.ctypes.data))
 
+    def SetPerFrameData(self, per_frame):
+        """idkptSetPerFrameData: one gputypes.GpuPerFrameData record, taken as it is (the library reads InvProjection, InvView and ViewPos)."""
+        p = np.ascontiguousarray(per_frame, T.GpuPerFrameData).reshape(-1)
+        if len(p) != 1:
+            raise ValueError("SetPerFrameData: one GpuPerFrameData record")
+        self._check(self._L.idkptSetPerFrameData(self._ctx, p.ctypes.data))
+
     def UpdateBuffer(self, which, array, offset_bytes=0):
         a = np.ascontiguousarray(array)
         self._check(self._L.idkptUpdateBuffer(self._ctx, which, offset_bytes, a.nbytes, a.ctypes.data))

@@ -237,6 +237,12 @@ class OraclePathTracer:
         ip = np.ascontiguousarray(cam.inv_projection, np.float32); iv = np.ascontiguousarray(cam.inv_view, np.float32); vp = np.ascontiguousarray(cam.position, np.float32)
         lib().ref_pt_set_perframe(self._pt, ip.ctypes.data, iv.ctypes.data, vp.ctypes.data)
 
+    def set_perframe_data(self, per_frame):
+        """The camera as the raw record a host hands to idkptSetPerFrameData (gputypes.GpuPerFrameData): its InvProjection, InvView and ViewPos bytes, nothing derived."""
+        p = np.ascontiguousarray(per_frame, self.T.GpuPerFrameData).reshape(-1)[0]
+        ip = np.ascontiguousarray(p["InvProjection"]); iv = np.ascontiguousarray(p["InvView"]); vp = np.ascontiguousarray(p["ViewPos"])
+        lib().ref_pt_set_perframe(self._pt, ip.ctypes.data, iv.ctypes.data, vp.ctypes.data)
+
     def set_positions(self, positions):
         p = np.ascontiguousarray(positions, np.float32)
         lib().ref_scene_set_positions(self._scene, p.ctypes.data, len(p))

@@ -37,7 +37,7 @@ WALK_CASES = [
     ("atrium60k_d5_sort", lambda b: S.atrium_scene(60000, b), S.atrium_camera, 256, 144, dict(RayDepth=5, DoRaySorting=1)),
     ("helmet_d5_aov", configs.helmet_scene, configs.helmet_camera, 320, 256, dict(RayDepth=5, OutputAOVs=1)),
     ("lucy_lens_d4", configs.lucy_scene, configs.lucy_camera, 240, 320, dict(RayDepth=4, FocalLength=9.0, LenseRadius=0.04)),
-    ("axis_aligned_rays", lambda b: S.cornell_scene(b, "mixed"), lambda w, h: S.Camera(w, h, position=(0.0, 0.0, 3.4), fovy_deg=1e-4), 64, 64, dict(RayDepth=3)),   # directions (0, 0, -1) up to rounding: 1/dir overflows -> not vouched for
+    ("axis_aligned_rays", lambda b: S.cornell_scene(b, "mixed"), lambda w, h: S.Camera(w, h, position=(0.0, 0.0, 3.4), fovy_deg=1e-4), 64, 64, dict(RayDepth=3)),   # directions (0, 0, -1) up to rounding: x / y around 1e-8, so 1/dir is huge but FINITE (tests/test_adversarial_rays_ref.py); non-finite 1/dir: tests/test_gpu_adversarial_rays.py
 ]
 
 
@@ -59,7 +59,7 @@ def test_packet_walk_equals_oracle(name, mk_scene, mk_cam, w, h, ov, oracle_mod,
     if name != "axis_aligned_rays":
         assert st["packet_packets"] > 0 and st["packet_node_steps"] > 0 and 0 < st["packet_live_lanes"] <= 64 * st["packet_node_steps"], st
     else:
-        assert st["packet_flagged_rays"] > 0                                        # non-finite 1/dir: every entering ray goes to the exact kernel
+        assert st["packet_flagged_rays"] > 0                                        # 1/dir is huge but finite here: what the packet walk hands to the exact kernel, it hands over by its other rules
     if name == "presplit_sort_d6":
         assert st["packet_flagged_rays"] > 1000                                     # the marked triangles cover most of the view
     if name == "soup100k_interior_d4":
