@@ -50,6 +50,7 @@ def lib():
         L.ref_pt_reset_accumulation.argtypes = [C.c_void_p]
         L.ref_pt_set_sample_sequence.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32]
         L.ref_pt_set_uv_hooks.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.ref_pt_set_branch_record.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.ref_pt_enable_counters.argtypes = [C.c_void_p, C.c_int]
         L.ref_pt_render.argtypes = [C.c_void_p]
         L.ref_pt_get_image.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
@@ -167,6 +168,12 @@ def trace_shadows(scene, params, depth, normal_oct, visibility=None, use_tlas=Fa
         L.ref_scene_destroy(C.c_void_p(h)); del keep
 
 
+# ref_pathtracer.cpp BR_*: the bits of one word of the branch record (OraclePathTracer.set_branch_record)
+BRANCH = {n: 1 << i for i, n in enumerate((
+    "shaded", "alpha_skip", "blend", "light", "inside", "absorb", "exp_underflow", "flip", "bsdf0", "bsdf1", "bsdf2", "tir", "thin", "metallic_lo", "metallic_hi", "roughness_lo",
+    "roughness_hi", "transmission_lo", "transmission_hi", "ior_lo", "absorbance_lo", "roulette", "sky", "throughput_subnormal", "throughput_zero", "on_bound", "chance_tie", "roulette_tie", "cos_zero"))}
+
+
 class OraclePathTracer:
     """Sequential CPU execution of the reference's FirstHit/NHit/FinalDraw schedule (PathTracer.cs:214-271)."""
 
@@ -262,6 +269,19 @@ class OraclePathTracer:
         written to dump[ray] and / or replaced by override[ray] where that is not NaN ((W * H, 2) float32 arrays the caller keeps alive); stage -1 switches both off."""
         self._uv_keep = (override, dump)
         lib().ref_pt_set_uv_hooks(self._pt, int(stage), None if override is None else override.ctypes.data, None if dump is None else dump.ctypes.data)
+
+    def set_branch_record(self, samples=1, bounces=None):
+        """Test hook: from now on every shaded hit writes its branch flags (BRANCH) and what it hit — (mesh id + 1) | MeshTransformId << 16, 0x80000000 | light index, 0 for the
+        sky — to the two returned uint32 arrays [sample, bounce, pixel]; sample counted from the last reset of the accumulation, bounce 0 = FirstHit, flags 0 where no ray was
+        shaded.  samples = 0 switches the record off.  The renderer's outputs do not depend on it."""
+        if not samples:
+            self._branch = None
+            lib().ref_pt_set_branch_record(self._pt, None, None, 0, 0)
+            return None
+        bounces = int(self.settings.RayDepth if bounces is None else bounces)
+        self._branch = (np.zeros((int(samples), bounces, self.rows * self.width), np.uint32), np.zeros((int(samples), bounces, self.rows * self.width), np.uint32))
+        lib().ref_pt_set_branch_record(self._pt, self._branch[0].ctypes.data, self._branch[1].ctypes.data, int(samples), bounces)
+        return self._branch
 
     def set_sample_sequence(self, first, stride):
         """idkptSetSampleSequence: sample i draws the reference's RNG streams of AccumulatedSamples = first + i * stride."""

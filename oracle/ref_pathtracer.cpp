@@ -383,6 +383,15 @@ static v3 SampleSky(const Scene& s, v3 d)
               gmix(gmix(t[0].z, t[1].z, wx), gmix(t[2].z, t[3].z, wx), wy));
 }
 
+// Branch record (test hook, ref_pt_set_branch_record): one word per shaded hit saying which branches of the shading it took.  Bits mirrored in oracle/oracle.py (BRANCH).
+enum : uint32_t { BR_SHADED = 1u << 0, BR_ALPHA_SKIP = 1u << 1, BR_BLEND = 1u << 2, BR_LIGHT = 1u << 3, BR_INSIDE = 1u << 4, BR_ABSORB = 1u << 5, BR_EXP_UNDERFLOW = 1u << 6,
+                 BR_FLIP = 1u << 7, BR_BSDF0 = 1u << 8, BR_BSDF1 = 1u << 9, BR_BSDF2 = 1u << 10, BR_TIR = 1u << 11, BR_THIN = 1u << 12,
+                 BR_METALLIC_LO = 1u << 13, BR_METALLIC_HI = 1u << 14, BR_ROUGHNESS_LO = 1u << 15, BR_ROUGHNESS_HI = 1u << 16, BR_TRANSMISSION_LO = 1u << 17, BR_TRANSMISSION_HI = 1u << 18,
+                 BR_IOR_LO = 1u << 19, BR_ABSORBANCE_LO = 1u << 20, BR_ROULETTE = 1u << 21, BR_SKY = 1u << 22, BR_THROUGHPUT_SUBNORMAL = 1u << 23, BR_THROUGHPUT_ZERO = 1u << 24,
+                 BR_ON_BOUND = 1u << 25, BR_CHANCE_TIE = 1u << 26, BR_ROULETTE_TIE = 1u << 27, BR_COS_ZERO = 1u << 28 };
+// BR_*_LO / _HI: the value before the clamp lay strictly outside; BR_ON_BOUND: a value before a clamp was exactly its bound; BR_CHANCE_TIE: the draw of SelectBsdf EQUALLED the
+// specular chance or the specular + transmission chance (`>` and `>=` part here); BR_ROULETTE_TIE: the roulette's draw equalled p; BR_COS_ZERO: cosTheta == 0 before the flip test
+
 // include/Surface.glsl
 struct Surface { v3 Albedo; float Alpha; v3 Normal; v3 Emissive; v3 Absorbance; float Metallic, Roughness, Transmission, IOR, AlphaCutoff; bool IsVolumetric, TintOnTransmissive; };
 static Surface GetDefaultSurface() // :25-47
@@ -409,8 +418,23 @@ static Surface GetSurface(const Scene& sc, const GpuMaterial& m, v2 uv) // :49-7
     s.AlphaCutoff = m.AlphaCutoff; s.IsVolumetric = m.IsVolumetric != 0; s.TintOnTransmissive = true;
     return s;
 }
-static void SurfaceApplyModificatons(Surface& s, const GpuMesh& mesh) // :79-91 (SURFACE_EMISSIVE_FACTOR 1.0)
+static void SurfaceApplyModificatons(Surface& s, const GpuMesh& mesh, uint32_t* rec = nullptr) // :79-91 (SURFACE_EMISSIVE_FACTOR 1.0)
 {
+    if (rec) {                                             // branch record only: reads the values the clamps below are about to see
+        const float a[3] = {s.Absorbance.x + mesh.AbsorbanceBias[0], s.Absorbance.y + mesh.AbsorbanceBias[1], s.Absorbance.z + mesh.AbsorbanceBias[2]};
+        const float m = s.Metallic + mesh.SpecularBias, r = s.Roughness + mesh.RoughnessBias, t = s.Transmission + mesh.TransmissionBias, i = s.IOR + mesh.IORBias;
+        if (a[0] < 0.0f || a[1] < 0.0f || a[2] < 0.0f) *rec |= BR_ABSORBANCE_LO;
+        if (m < 0.0f) *rec |= BR_METALLIC_LO;
+        if (m > 1.0f) *rec |= BR_METALLIC_HI;
+        if (r < 0.0f) *rec |= BR_ROUGHNESS_LO;
+        if (r > 1.0f) *rec |= BR_ROUGHNESS_HI;
+        if (t < 0.0f) *rec |= BR_TRANSMISSION_LO;
+        if (t > 1.0f) *rec |= BR_TRANSMISSION_HI;
+        if (i < 1.0f) *rec |= BR_IOR_LO;
+        if (mesh.SpecularBias != 0.0f && (m == 0.0f || m == 1.0f)) *rec |= BR_ON_BOUND;
+        if (mesh.RoughnessBias != 0.0f && (r == 0.0f || r == 1.0f)) *rec |= BR_ON_BOUND;
+        if (mesh.TransmissionBias != 0.0f && (t == 0.0f || t == 1.0f)) *rec |= BR_ON_BOUND;
+    }
     s.Emissive = s.Emissive * 1.0f + mesh.EmissiveBias * s.Albedo;
     s.Absorbance = V3(gmax(s.Absorbance.x + mesh.AbsorbanceBias[0], 0.0f), gmax(s.Absorbance.y + mesh.AbsorbanceBias[1], 0.0f), gmax(s.Absorbance.z + mesh.AbsorbanceBias[2], 0.0f));
     s.Metallic = gclamp(s.Metallic + mesh.SpecularBias, 0.0f, 1.0f);
@@ -424,7 +448,7 @@ static inline float GetSurfaceVariance(float spec, float trans, float rough) { f
 // PathTracing/include/Shading.glsl
 enum { BSDF_DIFFUSE = 0, BSDF_SPECULAR = 1, BSDF_TRANSMISSIVE = 2 };
 struct SampleMaterialResult { v3 RayDirection; uint32_t BsdfType; v3 Bsdf; float Pdf; float NewIor; };
-static SampleMaterialResult SampleMaterial(v3 incomming, Surface surface, float prevIor, bool fromInside, Rng* rng, uint32_t gidSeed, uint32_t accumulatedSamples) // :59-150
+static SampleMaterialResult SampleMaterial(v3 incomming, Surface surface, float prevIor, bool fromInside, Rng* rng, uint32_t gidSeed, uint32_t accumulatedSamples, uint32_t* rec = nullptr) // :59-150
 {
     surface.Roughness *= surface.Roughness;
     float cosTheta = dot(-incomming, surface.Normal);
@@ -438,6 +462,7 @@ static SampleMaterialResult SampleMaterial(v3 incomming, Surface surface, float 
     { // SelectBsdf :31-52
         float specularChance = surface.Metallic, transmissionChance = surface.Transmission;
         float rnd = rnd01(rng);
+        if (rec && (specularChance == rnd || specularChance + transmissionChance == rnd)) *rec |= BR_CHANCE_TIE;
         if (specularChance > rnd) result.BsdfType = BSDF_SPECULAR;
         else if (specularChance + transmissionChance > rnd) result.BsdfType = BSDF_TRANSMISSIVE;
         else result.BsdfType = BSDF_DIFFUSE;
@@ -459,11 +484,11 @@ static SampleMaterialResult SampleMaterial(v3 incomming, Surface surface, float 
     } else {
         result.NewIor = fromInside ? 1.0f : surface.IOR;
         v3 refr; bool tir;
-        if (!surface.IsVolumetric) { refr = incomming; tir = false; result.NewIor = 1.0f; }
+        if (!surface.IsVolumetric) { refr = incomming; tir = false; result.NewIor = 1.0f; if (rec) *rec |= BR_THIN; }
         else {
             refr = refract(incomming, surface.Normal, prevIor / result.NewIor);
             tir = (refr.x == 0.0f && refr.y == 0.0f && refr.z == 0.0f);
-            if (tir) { refr = reflect(incomming, surface.Normal); result.NewIor = prevIor; }
+            if (tir) { refr = reflect(incomming, surface.Normal); result.NewIor = prevIor; if (rec) *rec |= BR_TIR; }
         }
         refr = normalize(gmix(refr, !tir ? -diffuseRayDir : diffuseRayDir, surface.Roughness));
         result.RayDirection = refr;
@@ -472,13 +497,16 @@ static SampleMaterialResult SampleMaterial(v3 incomming, Surface surface, float 
         result.Pdf = 1.0f;
     }
     result.Pdf = gmax(result.Pdf, 0.0001f);
+    if (rec) *rec |= BR_BSDF0 << result.BsdfType;
     return result;
 }
 // PathTracing/include/RussianRoulette.glsl:3-12
-static bool RussianRouletteTerminateRay(v3& throughput, Rng* rng)
+static bool RussianRouletteTerminateRay(v3& throughput, Rng* rng, uint32_t* rec = nullptr)
 {
     float p = gmax(throughput.x, gmax(throughput.y, throughput.z));
-    if (rnd01(rng) > p) return true;
+    float rnd = rnd01(rng);
+    if (rec && rnd == p) *rec |= BR_ROULETTE_TIE;
+    if (rnd > p) return true;
     throughput = throughput / p;
     return false;
 }
@@ -504,6 +532,10 @@ struct PT {
     // test hooks (oracle/glref/fuzz_reference.py, the textured-stage check): in stage uvStage (0 = FirstHit, j = NHit j) the texture coordinate a ray interpolates is written to
     // uvDump[2 * rayIndex ..] and / or replaced by uvOverride[2 * rayIndex ..] where that is not NaN — the taps of the stage then read exactly the coordinates another execution read
     int uvStage = -1; const float* uvOverride = nullptr; float* uvDump = nullptr;
+    // test hook (ref_pt_set_branch_record): branchRec[((sample * recBounces + bounce) * pixels) + pixel] = BR_* flags of the hit that pixel's ray shaded in that bounce of that sample
+    // (sample counts from the last reset of the accumulation); 0 where no ray was shaded.  Written only; nothing the renderer computes reads it.
+    // branchWhat (optional, same index): (mesh id + 1) | MeshTransformId << 16 of a triangle hit, 0x80000000 | light index of a light hit, 0 for the sky
+    uint32_t* branchRec = nullptr; uint32_t* branchWhat = nullptr; int recSamples = 0, recBounces = 0;
     double parallelSec = 0.0, totalSec = 0.0;   // cpu_baseline leg of bench.py: time inside the per-invocation (OpenMP) sections / whole RenderSample
 };
 
@@ -528,6 +560,14 @@ static bool ShadeRay(PT& pt, bool first, GpuWavefrontRay& wr, GpuAovRay& ar, Rng
 {
     const Scene& s = *pt.scene;
     const GpuSettings& g = pt.st.Gpu;
+    uint32_t fl = BR_SHADED;
+    struct RecordOnExit { uint32_t* slot; const uint32_t& flags; ~RecordOnExit() { if (slot) *slot = flags; } } recordOnExit = {nullptr, fl};
+    if (pt.branchRec && stage >= 0 && stage < pt.recBounces && (int)pt.accumulated < pt.recSamples)
+        recordOnExit.slot = &pt.branchRec[((size_t)pt.accumulated * pt.recBounces + stage) * ((size_t)pt.W * pt.rows) + rayIndex];
+    uint32_t* rec = recordOnExit.slot ? &fl : nullptr;
+    uint32_t* what = (rec && pt.branchWhat) ? pt.branchWhat + (recordOnExit.slot - pt.branchRec) : nullptr;
+    auto noteThroughput = [&](v3 t) { if (!rec) return; const float c[3] = {t.x, t.y, t.z};
+                                      for (float x : c) { if (x == 0.0f) fl |= BR_THROUGHPUT_ZERO; else if (gabs(x) < 1.17549435e-38f) fl |= BR_THROUGHPUT_SUBNORMAL; } };
     v2 packed = {wr.PackedDirectionX, wr.PackedDirectionY};
     v3 rayDir = DecodeUnitVec(packed);
     v3 origin = V3(wr.Origin[0], wr.Origin[1], wr.Origin[2]);
@@ -561,10 +601,12 @@ static bool ShadeRay(PT& pt, bool first, GpuWavefrontRay& wr, GpuAovRay& ar, Rng
             const GpuMeshTransform& xf = s.xforms[hit.MeshTransformId];
             const GpuMesh& mesh = s.meshes[tri.MeshId];
             const GpuMaterial& mat = s.materials[mesh.MaterialId];
+            if (what) *what = (tri.MeshId + 1u) | (hit.MeshTransformId << 16);
             surface = GetSurface(s, mat, uv);
-            SurfaceApplyModificatons(surface, mesh);
+            SurfaceApplyModificatons(surface, mesh, rec);
             float alphaCutoff = (surface.AlphaCutoff == 2.0f) ? rnd01(rng) : surface.AlphaCutoff; // SurfaceHasAlphaBlending
-            if (surface.Alpha < alphaCutoff) { origin = origin + rayDir * 0.001f; store(); return true; }
+            if (surface.AlphaCutoff == 2.0f) fl |= BR_BLEND;
+            if (surface.Alpha < alphaCutoff) { fl |= BR_ALPHA_SKIP; origin = origin + rayDir * 0.001f; store(); return true; }
             v3 worldNormal = normalize(xform34_transposed3(xf.InvModel, interpNormal));
             v3 worldTangent = normalize(xform34_transposed3(xf.InvModel, interpTangent));
             v3 N = normalize(worldNormal), T = normalize(worldTangent), B = normalize(cross(N, T)); // Math.glsl:130-137 GetTBN
@@ -575,6 +617,7 @@ static bool ShadeRay(PT& pt, bool first, GpuWavefrontRay& wr, GpuAovRay& ar, Rng
             geometricNormal = normalize(xform34_transposed3(xf.InvModel, geometricNormal));
         } else if (g.DoTraceLights) {
             if (sortingKey) *sortingKey = hit.MeshTransformId;
+            fl |= BR_LIGHT; if (what) *what = 0x80000000u | hit.MeshTransformId;
             const GpuLight& l = s.lights[hit.MeshTransformId];
             surface.Emissive = V3(l.Color[0], l.Color[1], l.Color[2]); surface.Albedo = surface.Emissive;
             surface.Normal = (origin - V3(l.Position[0], l.Position[1], l.Position[2])) / l.Radius;
@@ -585,13 +628,21 @@ static bool ShadeRay(PT& pt, bool first, GpuWavefrontRay& wr, GpuAovRay& ar, Rng
         if (fromInside) {
             if (first) prevIor = surface.IOR;
             geometricNormal = geometricNormal * -1.0f;
-            if (surface.IsVolumetric) throughput = throughput * gexp3(-surface.Absorbance * hit.T);
+            fl |= BR_INSIDE;
+            if (surface.IsVolumetric) {
+                fl |= BR_ABSORB;
+                const v3 e = -surface.Absorbance * hit.T;
+                if (e.x < -87.0f || e.y < -87.0f || e.z < -87.0f) fl |= BR_EXP_UNDERFLOW;
+                throughput = throughput * gexp3(-surface.Absorbance * hit.T);
+            }
         }
         float cosTheta = dot(-rayDir, surface.Normal);
-        if (cosTheta < 0.0f) { surface.Normal = surface.Normal * -1.0f; cosTheta *= -1.0f; }
+        if (cosTheta == 0.0f) fl |= BR_COS_ZERO;
+        if (cosTheta < 0.0f) { surface.Normal = surface.Normal * -1.0f; cosTheta *= -1.0f; fl |= BR_FLIP; }
         radiance = radiance + surface.Emissive * throughput;
-        SampleMaterialResult result = SampleMaterial(rayDir, surface, prevIor, fromInside, rng, gidSeed, pt.sampleIndex());
+        SampleMaterialResult result = SampleMaterial(rayDir, surface, prevIor, fromInside, rng, gidSeed, pt.sampleIndex(), rec);
         throughput = throughput * (result.Bsdf / result.Pdf);
+        noteThroughput(throughput);
         {
             float weight = GetSurfaceVariance(surface.Metallic, surface.Transmission, surface.Roughness);
             if (first) { v3 a = surface.Albedo * weight, n = surface.Normal * weight; ar.Albedo[0] = a.x; ar.Albedo[1] = a.y; ar.Albedo[2] = a.z; ar.Normal[0] = n.x; ar.Normal[1] = n.y; ar.Normal[2] = n.z; ar.NewWeight = 1.0f - weight; }
@@ -602,8 +653,8 @@ static bool ShadeRay(PT& pt, bool first, GpuWavefrontRay& wr, GpuAovRay& ar, Rng
             }
         }
         if (!first) { // NHit:188-192
-            bool terminate = g.DoRussianRoulette && RussianRouletteTerminateRay(throughput, rng);
-            if (terminate) { store(); return false; }
+            bool terminate = g.DoRussianRoulette && RussianRouletteTerminateRay(throughput, rng, rec);
+            if (terminate) { fl |= BR_ROULETTE; store(); return false; }
         }
         if (result.BsdfType == BSDF_TRANSMISSIVE) geometricNormal = geometricNormal * -1.0f;
         origin = origin + geometricNormal * 0.001f;
@@ -613,6 +664,7 @@ static bool ShadeRay(PT& pt, bool first, GpuWavefrontRay& wr, GpuAovRay& ar, Rng
         store();
         return true;
     } else {
+        fl |= BR_SKY;
         v3 albedo = SampleSky(s, rayDir);
         v3 fn = CubemapFaceNormal(rayDir);
         if (first) { ar.Albedo[0] = albedo.x; ar.Albedo[1] = albedo.y; ar.Albedo[2] = albedo.z; ar.Normal[0] = fn.x; ar.Normal[1] = fn.y; ar.Normal[2] = fn.z; }
@@ -947,6 +999,8 @@ void ref_pt_set_settings(void* p, const idkpt_settings* s) { ((PT*)p)->st = *s; 
 void ref_pt_set_perframe(void* p, const float* invProj, const float* invView, const float* viewPos) { PT* pt = (PT*)p; memcpy(pt->invProj, invProj, 64); memcpy(pt->invView, invView, 64); memcpy(pt->viewPos, viewPos, 12); }
 void ref_pt_reset_accumulation(void* p) { ((PT*)p)->accumulated = 0; }
 void ref_pt_set_uv_hooks(void* p, int stage, const float* overrideUv, float* dumpUv) { PT* pt = (PT*)p; pt->uvStage = stage; pt->uvOverride = overrideUv; pt->uvDump = dumpUv; }   // test hooks (struct PT)
+// test hook (struct PT): flags = uint32[samples * bounces * pixels] the caller keeps alive and has zeroed, or NULL to switch the record off
+void ref_pt_set_branch_record(void* p, uint32_t* flags, uint32_t* what, int samples, int bounces) { PT* pt = (PT*)p; pt->branchRec = flags; pt->branchWhat = flags ? what : nullptr; pt->recSamples = flags ? samples : 0; pt->recBounces = flags ? bounces : 0; }
 void ref_pt_set_sample_sequence(void* p, uint32_t first, uint32_t stride) { PT* pt = (PT*)p; pt->seqFirst = first; pt->seqStride = stride; pt->accumulated = 0; }
 void ref_pt_enable_counters(void* p, int on) { ((PT*)p)->countersOn = on != 0; }
 void ref_pt_render(void* p) { PT* pt = (PT*)p; for (int i = 0; i < pt->st.SamplesPerPixel; i++) RenderSample(*pt); } // PathTracer.cs:218
