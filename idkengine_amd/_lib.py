@@ -18,6 +18,7 @@ SYMBOLS = [
     "idkptSetStream", "idkptGetStream", "idkptSetDeveloperOption", "idkptSetMaxBatch", "idkptFlush", "idkptTraceRays", "idkptTraceShadows", "idkptTraceRaysDevice", "idkptTraceShadowsDevice", "idkptSetFrameRing", "idkptBeginFrame", "idkptDownloadFrame", "idkptGetFrameDevicePtr",
     "idkptPresent", "idkptDownloadDisplay", "idkptGetDisplayDevicePtr",
     "idkptBloom", "idkptGetBloomInfo", "idkptDownloadBloom", "idkptGetBloomDevicePtr",
+    "idkptSetPresentationSize", "idkptGetPresentationSize", "idkptGetBloomRoute", "idkptGetBloomChainDevicePtr",
 ]
 
 _lib = None
@@ -46,6 +47,7 @@ def load():
         "idkptDownloadFrame": [vp, i32, i32, vp, sz], "idkptGetFrameDevicePtr": [vp, i32, i32, C.POINTER(vp), C.POINTER(sz)],
         "idkptPresent": [vp, i32, i32, vp, i32, vp, vp], "idkptDownloadDisplay": [vp, i32, vp, sz], "idkptGetDisplayDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(sz)],
         "idkptBloom": [vp, i32, i32, vp], "idkptGetBloomInfo": [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)], "idkptDownloadBloom": [vp, i32, i32, i32, vp, sz], "idkptGetBloomDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(sz)],
+        "idkptSetPresentationSize": [vp, i32, i32], "idkptGetPresentationSize": [vp, C.POINTER(i32), C.POINTER(i32)], "idkptGetBloomRoute": [vp, i32, C.POINTER(i32)], "idkptGetBloomChainDevicePtr": [vp, i32, i32, C.POINTER(vp), C.POINTER(sz)],
         "idkptRefitBlas": [vp, i32], "idkptUploadUnskinnedVertices": [vp, vp, i32], "idkptSkin": [vp, u32, u32, u32, u32],
         "idkptDownloadBuffer": [vp, i32, sz, sz, vp], "idkptResetAccumulation": [vp], "idkptSetSampleSequence": [vp, u32, u32], "idkptGetAccumulatedSamples": [vp, C.POINTER(u32)],
         "idkptRender": [vp], "idkptSynchronize": [vp], "idkptDownload": [vp, i32, vp, sz], "idkptDownloadRays": [vp, vp, sz],
@@ -55,6 +57,8 @@ def load():
         "idkptSetStream": [vp, vp], "idkptGetStream": [vp, C.POINTER(vp)], "idkptSetDeveloperOption": [vp, C.c_char_p, i32], "idkptSetMaxBatch": [vp, i32], "idkptFlush": [vp],
     }
     for name, args in sig.items():
+        if not hasattr(L, name) and os.environ.get("IDKPT_LIB_PATH"):
+            continue                                   # (an older build in an A/B run lacks the newest entry points: calling one raises AttributeError)
         fn = getattr(L, name)
         fn.argtypes = args
         fn.restype = i32

@@ -3,6 +3,7 @@
 // Behaves as idkptPresent does (host_readback.hpp): queued samples are launched first, nothing waits for the GPU, buffers belong to a ring slot and a frame size —
 // three per slot (the down chain, the up chain: RGBA16F levels one behind the other; the expanded RGBA32F image), allocated at the slot's first bloom, released by
 // alloc_frame_impl, kept by idkptSetMaxBatch, each followed by BLOOM_GUARD_BYTES of 0xA5 that nothing writes.
+// The chain and the expanded image have the presentation size (host_readback.hpp pres_w / pres_h; the render size by default), the image they start from the render size.
 // One device, the whole frame: bloom is a global filter (the last level mixes the whole image), a shard of the rows would need halos as wide as the chain.
 #pragma once
 
@@ -36,13 +37,17 @@ static int32_t dev_Bloom(dev_ctx* ctx, int32_t slot, int32_t image, const idkpt_
     REQUIRE(fin(b->Threshold) && fin(b->MaxColor), "idkptBloom: Threshold and MaxColor must be finite");
     REQUIRE(b->MinusLods >= 0, "idkptBloom: MinusLods must not be negative");
     if (ctx->W <= 0 || !ctx->frameOk) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptBloom: no frame buffers (idkptSetSize not called)");
+    if (present_scaled(ctx) && (ctx->grouped || !holds_whole_frame(ctx)))
+        return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptBloom: a presentation size other than the render size (idkptSetPresentationSize) needs one device that holds the whole frame; this context holds a shard of the rows");
     if (ctx->rowMod != 1 || ctx->rowRem != 0 || ctx->rows != ctx->H) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptBloom: the context holds a shard of the rows (idkptSetRowSharding / idkptSetRowBands / idkptSetRowRange); bloom needs the whole frame on one device");
-    if (ctx->W < 2 || ctx->H < 2) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptBloom: the frame must be at least 2 x 2 (level 0 is width / 2 x height / 2)");
+    // the chain is sized from the PRESENTATION size (Bloom.SetSize(presentRes), Application.cs:570-586), which is the render size unless idkptSetPresentationSize said otherwise
+    const int W = ctx->W, H = ctx->H, pw = pres_w(ctx), ph = pres_h(ctx);
+    if (pw < 2 || ph < 2) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptBloom: the frame must be at least 2 x 2 (level 0 is width / 2 x height / 2)");
     if (slot < 0) slot = ctx->curSlot;
-    const int W = ctx->W, H = ctx->H;
     int w0 = 0, h0 = 0;
-    const int levels = bloomt::bloom_levels(W, H, b->MinusLods, &w0, &h0);
-    if (!bloom_tile_spans_fit(w0, W) || !bloom_tile_spans_fit(h0, H)) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptBloom: internal: a tile of down pass 0 reads more source texels than it stages");
+    const int levels = bloomt::bloom_levels(pw, ph, b->MinusLods, &w0, &h0);
+    // a render size up to the presentation size (and the equal sizes of a context without one) always fits the staged tile; a larger one (supersampling) may not
+    const bool direct = !bloom_tile_spans_fit(w0, W) || !bloom_tile_spans_fit(h0, H);
     HIPC(hipSetDevice(ctx->device));
     FLUSH_KEEP();                                        // stream-ordered behind what was queued (as idkptPresent)
     { int rc = check_overflow(ctx); if (rc) return rc; }   // (no wait: see idkptGetFrameDevicePtr)
@@ -51,12 +56,13 @@ static int32_t dev_Bloom(dev_ctx* ctx, int32_t slot, int32_t image, const idkpt_
     s.valid = false;
     { int rc = bloom_ensure(ctx, s.down, s.downBytes, bloom_level_offset(w0, h0, levels) * 8); if (rc) return rc; }
     { int rc = bloom_ensure(ctx, s.up, s.upBytes, bloom_level_offset(w0, h0, levels - 1) * 8); if (rc) return rc; }
-    { int rc = bloom_ensure(ctx, s.out, s.outBytes, (size_t)W * H * 16); if (rc) return rc; }
+    { int rc = bloom_ensure(ctx, s.out, s.outBytes, (size_t)pw * ph * 16); if (rc) return rc; }
     auto lvl = [&](DevBuf& buf, int l) { return (uint2*)buf.p + bloom_level_offset(w0, h0, l); };
     auto dim = [](int d0, int l) { return bloomt::level_dim(d0, l); };
     auto grid = [](int w, int h) { return dim3((unsigned)((w + bloomk::TILE - 1) / bloomk::TILE), (unsigned)((h + bloomk::TILE - 1) / bloomk::TILE)); };
     // down pass 0: the image, Lod 0, Prefilter -> down level 0
-    hipLaunchKernelGGL(k_bloom_down0, grid(w0, h0), dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, image, slot), W, H, lvl(s.down, 0), w0, h0, b->MaxColor, b->Threshold);
+    if (direct) hipLaunchKernelGGL(k_bloom_down0_direct, grid(w0, h0), dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, image, slot), W, H, lvl(s.down, 0), w0, h0, b->MaxColor, b->Threshold);
+    else hipLaunchKernelGGL(k_bloom_down0, grid(w0, h0), dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, image, slot), W, H, lvl(s.down, 0), w0, h0, b->MaxColor, b->Threshold);
     // down pass l: down level l - 1 -> down level l; Lod = l - 1, so the pass that writes level 1 prefilters again (compute.glsl:41, Bloom.cs:85)
     for (int l = 1; l < levels; l++)
         hipLaunchKernelGGL((k_bloom_pass<0>), grid(dim(w0, l), dim(h0, l)), dim3(256), 0, ctx->stream, (const uint2*)lvl(s.down, l - 1), (const uint2*)nullptr, dim(w0, l - 1), dim(h0, l - 1), lvl(s.down, l), dim(w0, l), dim(h0, l), l == 1 ? 1 : 0, b->MaxColor, b->Threshold);
@@ -65,9 +71,9 @@ static int32_t dev_Bloom(dev_ctx* ctx, int32_t slot, int32_t image, const idkpt_
         const uint2* a = l == levels - 2 ? lvl(s.down, l + 1) : lvl(s.up, l + 1);
         hipLaunchKernelGGL((k_bloom_pass<1>), grid(dim(w0, l), dim(h0, l)), dim3(256), 0, ctx->stream, a, (const uint2*)lvl(s.down, l + 1), dim(w0, l + 1), dim(h0, l + 1), lvl(s.up, l), dim(w0, l), dim(h0, l), 0, 0.0f, 0.0f);
     }
-    hipLaunchKernelGGL(k_bloom_expand, dim3((unsigned)(((size_t)W * H + 255) / 256)), dim3(256), 0, ctx->stream, (const uint2*)lvl(s.up, 0), w0, h0, (float4*)s.out.p, W, H);
+    hipLaunchKernelGGL(k_bloom_expand, dim3((unsigned)(((size_t)pw * ph + 255) / 256)), dim3(256), 0, ctx->stream, (const uint2*)lvl(s.up, 0), w0, h0, (float4*)s.out.p, pw, ph);
     HIPC(hipGetLastError());
-    s.levels = levels; s.w0 = w0; s.h0 = h0; s.valid = true;
+    s.levels = levels; s.w0 = w0; s.h0 = h0; s.direct = direct; s.valid = true;
     return IDKPT_OK;
 }
 // the last bloom of a slot; INVALID_OPERATION when the slot was not bloomed since the last resize
@@ -87,6 +93,25 @@ static int32_t dev_GetBloomInfo(dev_ctx* ctx, int32_t slot, int32_t* levels, int
     if (levels) *levels = s->levels;
     if (w0) *w0 = s->w0;
     if (h0) *h0 = s->h0;
+    return IDKPT_OK;
+}
+// a whole chain as it lies in memory (the levels one behind the other, level 0 first): *outBytes in front of the chain's guard
+static int32_t dev_GetBloomChainDevicePtr(dev_ctx* ctx, int32_t slot, int32_t chain, void** outPtr, size_t* outBytes)
+{
+    if (!ctx || !outPtr) return IDKPT_ERR_INVALID_ARGUMENT;
+    REQUIRE(chain == 0 || chain == 1, "idkptGetBloomChainDevicePtr: chain must be 0 (down) or 1 (up)");
+    BloomSlot* s = nullptr;
+    { int rc = bloom_of(ctx, "idkptGetBloomChainDevicePtr", slot, &s); if (rc) return rc; }
+    *outPtr = chain ? s->up.p : s->down.p;
+    if (outBytes) *outBytes = chain ? s->upBytes : s->downBytes;
+    return IDKPT_OK;
+}
+static int32_t dev_GetBloomRoute(dev_ctx* ctx, int32_t slot, int32_t* route)
+{
+    if (!ctx || !route) return IDKPT_ERR_INVALID_ARGUMENT;
+    BloomSlot* s = nullptr;
+    { int rc = bloom_of(ctx, "idkptGetBloomRoute", slot, &s); if (rc) return rc; }
+    *route = s->direct ? IDKPT_BLOOM_ROUTE_DIRECT : IDKPT_BLOOM_ROUTE_TILED;
     return IDKPT_OK;
 }
 static int32_t dev_DownloadBloom(dev_ctx* ctx, int32_t slot, int32_t chain, int32_t level, void* dst, size_t bytes)

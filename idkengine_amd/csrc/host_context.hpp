@@ -14,6 +14,7 @@ struct DevBuf {
 struct BloomSlot {
     DevBuf down, up, out; size_t downBytes = 0, upBytes = 0, outBytes = 0;   // (bytes in front of each buffer's guard)
     int levels = 0, w0 = 0, h0 = 0; bool valid = false;                      // valid: bloomed since the last resize
+    bool direct = false;                                                     // down pass 0 of the last bloom fetched from memory (k_bloom_down0_direct) instead of staging tiles
     void release() { down.release(); up.release(); out.release(); downBytes = upBytes = outBytes = 0; valid = false; }
 };
 
@@ -164,6 +165,7 @@ struct dev_ctx {
     DevBuf img[3];
     std::vector<DevBuf> disp; std::vector<int> dispFmt;   // idkptPresent: the display image of every ring slot (allocated at the first present of the slot) and its format (enum idkpt_display_format; -1: not presented since the last resize)
     std::vector<BloomSlot> bloom;   // idkptBloom: per ring slot, allocated at the slot's first bloom
+    int presW = 0, presH = 0;       // idkptSetPresentationSize: the size of the display and bloom images (0, 0: the render size); a state of its own, kept by every resize
     DevBuf camTab;                                       // per-sample cameras of the batch being launched (ring mode)
     int rowLimit = 0x7fffffff;                           // idkptSetRowRange: at most this many local rows
     idkpt_bounce_exchange_fn exchangeFn = nullptr; void* exchangeUser = nullptr;   // exact multi-GPU deep paths (idkptSetBounceExchange)

@@ -176,6 +176,35 @@ static int32_t dev_GetStream(dev_ctx* ctx, void** out) { if (!ctx || !out) retur
 // row tail never ran past the image).
 #define DISPLAY_GUARD_BYTES 64
 static size_t display_texel_bytes(int format) { return format == IDKPT_DISPLAY_RGBA32F ? 16 : 4; }
+// The presentation size (idkptSetPresentationSize): the size of the display image and of bloom's chain and expanded image.  (0, 0) follows the render size.  While it equals
+// the render size idkptPresent / idkptBloom run exactly what they ran before there was one; when it differs (present_scaled) the scaled kernels run, on one device with the
+// whole frame only.
+static int pres_w(const dev_ctx* ctx) { return ctx->presW ? ctx->presW : ctx->W; }
+static int pres_h(const dev_ctx* ctx) { return ctx->presW ? ctx->presH : ctx->H; }
+static bool present_scaled(const dev_ctx* ctx) { return ctx->presW && (ctx->presW != ctx->W || ctx->presH != ctx->H); }
+static bool holds_whole_frame(const dev_ctx* ctx) { return ctx->rowMod == 1 && ctx->rowRem == 0 && ctx->rows == ctx->H; }
+static size_t display_texels(const dev_ctx* ctx) { return present_scaled(ctx) ? (size_t)ctx->presW * ctx->presH : (size_t)ctx->W * ctx->rows; }
+static int32_t dev_SetPresentationSize(dev_ctx* ctx, int32_t width, int32_t height)
+{
+    if (!ctx) return IDKPT_ERR_INVALID_ARGUMENT;
+    REQUIRE((width == 0 && height == 0) || (width > 0 && height > 0 && width <= 65536 && height <= 65536), "idkptSetPresentationSize: width and height must both be 0 (the render size) or both be 1..65536");
+    if (width == ctx->presW && height == ctx->presH) return IDKPT_OK;
+    HIPC(hipSetDevice(ctx->device));
+    // neither the images nor the accumulation are touched, nothing queued is launched: only what has the presentation size goes, and is re-made at its next use
+    for (DevBuf& b : ctx->disp) b.release();
+    ctx->disp.clear(); ctx->dispFmt.clear();
+    for (BloomSlot& s : ctx->bloom) s.release();
+    ctx->bloom.clear();
+    ctx->presW = width; ctx->presH = height;
+    return IDKPT_OK;
+}
+static int32_t dev_GetPresentationSize(dev_ctx* ctx, int32_t* width, int32_t* height)
+{
+    if (!ctx) return IDKPT_ERR_INVALID_ARGUMENT;
+    if (width) *width = pres_w(ctx);
+    if (height) *height = pres_h(ctx);
+    return IDKPT_OK;
+}
 // everything idkptPresent refuses before anything is launched (shared with the multi-device layer)
 static int32_t present_validate(dev_ctx* ctx, int32_t slot, int32_t image, const idkpt_tonemap* tm, int32_t format)
 {
@@ -185,6 +214,8 @@ static int32_t present_validate(dev_ctx* ctx, int32_t slot, int32_t image, const
     auto fin = [](float v) { return v - v == 0.0f; };
     REQUIRE(fin(tm->Exposure) && fin(tm->Saturation) && fin(tm->Linear) && fin(tm->Peak) && fin(tm->Compression), "idkptPresent: Exposure, Saturation, Linear, Peak and Compression must be finite");
     if (ctx->W <= 0 || !ctx->frameOk) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptPresent: no frame buffers (idkptSetSize not called)");
+    if (present_scaled(ctx) && (ctx->grouped || !holds_whole_frame(ctx)))
+        return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptPresent: a presentation size other than the render size (idkptSetPresentationSize) needs one device that holds the whole frame; this context is a member of a multi-device context or holds a shard of the rows");
     return IDKPT_OK;
 }
 static int32_t dev_Present(dev_ctx* ctx, int32_t slot, int32_t image, const idkpt_tonemap* tm, int32_t format, const void* dAdd0, const void* dAdd1)
@@ -195,7 +226,8 @@ static int32_t dev_Present(dev_ctx* ctx, int32_t slot, int32_t image, const idkp
     HIPC(hipSetDevice(ctx->device));
     FLUSH_KEEP();                                        // stream-ordered behind what was queued; the frame is complete without the deferred bounce's continuation (finish_deferred)
     { int rc = check_overflow(ctx); if (rc) return rc; }   // (no wait: see idkptGetFrameDevicePtr)
-    const size_t N = (size_t)ctx->W * ctx->rows, imageBytes = N * display_texel_bytes(format);
+    const bool scaled = present_scaled(ctx);
+    const size_t imageBytes = display_texels(ctx) * display_texel_bytes(format);
     if (ctx->disp.size() != (size_t)ctx->ringSize) { ctx->disp.resize(ctx->ringSize); ctx->dispFmt.assign(ctx->ringSize, -1); }
     DevBuf& buf = ctx->disp[slot];
     if (!buf.p || buf.bytes < imageBytes + DISPLAY_GUARD_BYTES) { ctx->dispFmt[slot] = -1; HIPC(buf.ensure(imageBytes + DISPLAY_GUARD_BYTES)); }
@@ -204,8 +236,13 @@ static int32_t dev_Present(dev_ctx* ctx, int32_t slot, int32_t image, const idkp
     presentk::present_setup(tm->Exposure, tm->Compression, &p);
     p.saturation = tm->Saturation; p.linear = tm->Linear; p.peak = tm->Peak; p.doTonemap = tm->DoTonemapAndSrgbTransform != 0;
     p.W = ctx->W; p.rows = ctx->rows; p.rowMod = ctx->rowMod; p.rowRem = ctx->rowRem; p.bandLog2 = ctx->rowBandLog2;
-    const uint32_t threads = (uint32_t)(((size_t)ctx->W + 3) / 4 * ctx->rows);
-    if (threads) {
+    if (scaled) { p.W = ctx->presW; p.rows = ctx->presH; }      // (the whole frame on this device: present_validate)
+    const uint32_t threads = (uint32_t)(((size_t)p.W + 3) / 4 * p.rows);
+    if (threads && scaled) {
+        if (format == IDKPT_DISPLAY_RGBA32F) hipLaunchKernelGGL((k_present_scaled<true>), dim3((threads + 255u) / 256u), dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, image, slot), ctx->W, ctx->H, (const float4*)dAdd0, (const float4*)dAdd1, buf.p, p);
+        else hipLaunchKernelGGL((k_present_scaled<false>), dim3((threads + 255u) / 256u), dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, image, slot), ctx->W, ctx->H, (const float4*)dAdd0, (const float4*)dAdd1, buf.p, p);
+        HIPC(hipGetLastError());
+    } else if (threads) {
         if (format == IDKPT_DISPLAY_RGBA32F) hipLaunchKernelGGL((k_present<true>), dim3((threads + 255u) / 256u), dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, image, slot), (const float4*)dAdd0, (const float4*)dAdd1, buf.p, p);
         else hipLaunchKernelGGL((k_present<false>), dim3((threads + 255u) / 256u), dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, image, slot), (const float4*)dAdd0, (const float4*)dAdd1, buf.p, p);
         HIPC(hipGetLastError());
@@ -219,7 +256,7 @@ static int32_t display_of(dev_ctx* ctx, const char* who, int32_t slot, int32_t* 
     REQUIRE(slot >= -1 && slot < ctx->ringSize, std::string(who) + ": slot outside the frame ring (-1: the current slot)");
     if (slot < 0) slot = ctx->curSlot;
     if ((size_t)slot >= ctx->dispFmt.size() || ctx->dispFmt[slot] < 0) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, std::string(who) + ": the slot was not presented since the last resize (idkptPresent)");
-    *outSlot = slot; *outBytes = (size_t)ctx->W * ctx->rows * display_texel_bytes(ctx->dispFmt[slot]);
+    *outSlot = slot; *outBytes = display_texels(ctx) * display_texel_bytes(ctx->dispFmt[slot]);
     return IDKPT_OK;
 }
 static int32_t dev_DownloadDisplay(dev_ctx* ctx, int32_t slot, void* dst, size_t bytes)
@@ -227,7 +264,7 @@ static int32_t dev_DownloadDisplay(dev_ctx* ctx, int32_t slot, void* dst, size_t
     if (!ctx || !dst) return IDKPT_ERR_INVALID_ARGUMENT;
     size_t need = 0;
     { int rc = display_of(ctx, "idkptDownloadDisplay", slot, &slot, &need); if (rc) return rc; }
-    REQUIRE(bytes == need, "idkptDownloadDisplay: bytes must equal localRows*width*4 (RGBA8) or localRows*width*16 (RGBA32F)");
+    REQUIRE(bytes == need, "idkptDownloadDisplay: bytes must equal localRows*width*4 (RGBA8) or localRows*width*16 (RGBA32F), rows and width of the presentation size where one is set");
     HIPC(hipSetDevice(ctx->device));
     FLUSH_KEEP();
     HIPC(hipMemcpyAsync(dst, ctx->disp[slot].p, need, hipMemcpyDeviceToHost, ctx->stream));

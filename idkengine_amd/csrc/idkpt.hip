@@ -34,8 +34,8 @@ using namespace ptd;
 #include "kernels_texture.hpp"
 #include "kernels_sky.hpp"
 #include "kernels_unproject.hpp"
-#include "kernels_present.hpp"
 #include "kernels_bloom.hpp"
+#include "kernels_present.hpp"
 #include "bvh_gpu.hpp"
 #include "bvh_gpu_full.hpp"
 

@@ -808,6 +808,18 @@ int32_t idkptGetFrameDevicePtr(idkpt_ctx* c, int32_t slot, int32_t image, void**
     return group_gather_device(c, image, slot, outPtr, outBytes);
 }
 
+// the presentation size: a state of every member (each refuses a scaled present or bloom of its own rows); nothing is launched, nothing re-laid out
+int32_t idkptSetPresentationSize(idkpt_ctx* c, int32_t width, int32_t height)
+{
+    if (!c) return IDKPT_ERR_INVALID_ARGUMENT;
+    ONE(dev_SetPresentationSize(m, width, height));
+    GREQ((width == 0 && height == 0) || (width > 0 && height > 0 && width <= 65536 && height <= 65536), "idkptSetPresentationSize: width and height must both be 0 (the render size) or both be 1..65536");
+    ALL(dev_SetPresentationSize(m, width, height));
+    (void)hipSetDevice(c->dev[0]->device);
+    return IDKPT_OK;
+}
+int32_t idkptGetPresentationSize(idkpt_ctx* c, int32_t* width, int32_t* height) { if (!c) return IDKPT_ERR_INVALID_ARGUMENT; return dev_GetPresentationSize(c->dev[0], width, height); }
+
 // ---- the display image: every member presents its own rows (the dither is indexed with image rows: k_present), downloads and gathers are those of the images
 int32_t idkptPresent(idkpt_ctx* c, int32_t slot, int32_t image, const idkpt_tonemap* tonemap, int32_t format, const void* dAdd0, const void* dAdd1)
 {
@@ -842,7 +854,15 @@ int32_t idkptGetDisplayDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size
 
 // ---- bloom (host_bloom.hpp): one device, the whole frame — a global filter; a shard of the rows would need halos as wide as the chain
 #define BLOOM_ONE(who, call) do { if (!c) return IDKPT_ERR_INVALID_ARGUMENT; ONE(call); return gfail(c, IDKPT_ERR_INVALID_OPERATION, who ": bloom runs on one device with the whole frame; a multi-device context has none"); } while (0)
-int32_t idkptBloom(idkpt_ctx* c, int32_t slot, int32_t image, const idkpt_bloom* bloom) { BLOOM_ONE("idkptBloom", dev_Bloom(m, slot, image, bloom)); }
+int32_t idkptBloom(idkpt_ctx* c, int32_t slot, int32_t image, const idkpt_bloom* bloom)
+{
+    if (!c) return IDKPT_ERR_INVALID_ARGUMENT;
+    ONE(dev_Bloom(m, slot, image, bloom));
+    if (present_scaled(c->dev[0])) return gfail(c, IDKPT_ERR_INVALID_OPERATION, "idkptBloom: a presentation size other than the render size (idkptSetPresentationSize) needs one device that holds the whole frame; a multi-device context has none");
+    return gfail(c, IDKPT_ERR_INVALID_OPERATION, "idkptBloom: bloom runs on one device with the whole frame; a multi-device context has none");
+}
+int32_t idkptGetBloomChainDevicePtr(idkpt_ctx* c, int32_t slot, int32_t chain, void** outPtr, size_t* outBytes) { BLOOM_ONE("idkptGetBloomChainDevicePtr", dev_GetBloomChainDevicePtr(m, slot, chain, outPtr, outBytes)); }
+int32_t idkptGetBloomRoute(idkpt_ctx* c, int32_t slot, int32_t* route) { BLOOM_ONE("idkptGetBloomRoute", dev_GetBloomRoute(m, slot, route)); }
 int32_t idkptGetBloomInfo(idkpt_ctx* c, int32_t slot, int32_t* levels, int32_t* w0, int32_t* h0) { BLOOM_ONE("idkptGetBloomInfo", dev_GetBloomInfo(m, slot, levels, w0, h0)); }
 int32_t idkptDownloadBloom(idkpt_ctx* c, int32_t slot, int32_t chain, int32_t level, void* dst, size_t bytes) { BLOOM_ONE("idkptDownloadBloom", dev_DownloadBloom(m, slot, chain, level, dst, bytes)); }
 int32_t idkptGetBloomDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size_t* outBytes) { BLOOM_ONE("idkptGetBloomDevicePtr", dev_GetBloomDevicePtr(m, slot, outPtr, outBytes)); }

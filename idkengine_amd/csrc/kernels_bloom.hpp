@@ -9,12 +9,16 @@
 //    with offset +2; slot k of a tile row holds source texel clamp(lo + k): indices are clamped when the tile is FILLED, so a tap reads slot (unclamped index - lo)
 //    and gets exactly the texel a clamped fetch from memory returns, at image edges and for odd sizes.  16 outputs span at most (16 - 1) * W / w0 + 7 <= 38 texels
 //    (W <= 2 w0 + 1), so 40 x 40 slots (25.6 KB) hold every tile; the host checks the spans of a size before the first launch (host_bloom.hpp) and a slot index is
-//    clamped into the tile besides.
+//    clamped into the tile besides.  With a presentation size (idkptSetPresentationSize) the image keeps the RENDER size while level 0 is half the PRESENTATION size:
+//    uv still comes from the written level, so the same kernel reads the smaller image (render <= presentation, the engine's range: the spans only shrink).
+//  * k_bloom_down0_direct: the same pass for a render size so much LARGER than the presentation size that a tile's taps span more than 40 texels (supersampling):
+//    the same down_texel through a clamped fetch from memory, one 16-byte load per tap texel.  The host selects it when bloom_tile_spans_fit says no.
 //  * k_bloom_pass<MODE>: every other pass, from RGBA16F levels (8-byte texel loads): MODE 0 = Downsample of down level l - 1 (with Prefilter for l = 1: the
 //    reference uploads Lod = 0 for that pass too, and the shader prefilters `if (Lod == 0)`), MODE 1 = Upsample of the up (first up
 //    pass: the down) level l + 1 plus one tap of down level l + 1.  The levels are a quarter of the frame and smaller: they stay in L2.
 //  * k_bloom_expand: what the tonemap shader's texture(Sampler1, uv) reads, for every pixel of the frame — up level 0 magnified bilinearly — as an RGBA32F image
-//    (rgb, 1.0): idkptPresent's dAdd0.  One thread per pixel, a wave writes 1 KB of contiguous bytes.
+//    (rgb, 1.0): idkptPresent's dAdd0.  One thread per pixel, a wave writes 1 KB of contiguous bytes.  W x H is the PRESENTATION size (the size of the tonemap
+//    shader's ImgResult), which is the render size unless idkptSetPresentationSize said otherwise.
 // One launch per pass on the context's stream; a pass reads only what earlier launches wrote (no level is produced and consumed inside one launch).
 #pragma once
 #include "bloom_texel.hpp"
@@ -49,6 +53,15 @@ struct DevHalfLevel {             // an RGBA16F level in memory, one 8-byte load
         return bloomt::v3(bloomt::f16_to_f32((uint16_t)(q.x & 0xffffu)), bloomt::f16_to_f32((uint16_t)(q.x >> 16)), bloomt::f16_to_f32((uint16_t)(q.y & 0xffffu)));
     }
 };
+struct DevFloatImage {            // an RGBA32F image in memory (the path tracer's result), one 16-byte load per texel
+    const float4* p; int w, h;
+    DEV bloomt::V3 operator()(int x, int y) const
+    {
+        x = min(max(x, 0), w - 1); y = min(max(y, 0), h - 1);
+        const float4 q = p[(size_t)y * (size_t)w + (size_t)x];
+        return bloomt::v3(q.x, q.y, q.z);
+    }
+};
 // imageStore(ImgResult, imgCoord, vec4(result, 1.0)) to an RGBA16F level
 DEV uint2 pack_half4(bloomt::V3 v)
 {
@@ -76,6 +89,16 @@ __global__ __launch_bounds__(256) void k_bloom_down0(const float4* __restrict__ 
     const int x = tx0 + (tid & (TILE - 1)), y = ty0 + (tid >> 4);
     if (x >= dw || y >= dh) return;
     const LdsTile f = {tile, lox, loy};
+    dst[(size_t)y * (size_t)dw + (size_t)x] = pack_half4(bloomt::down_texel(f, W, H, x, y, dw, dh, true, maxColor, threshold));
+}
+
+// the same pass without the staged tile (grid and thread mapping of k_bloom_pass): every tap texel is a clamped fetch from memory
+__global__ __launch_bounds__(256) void k_bloom_down0_direct(const float4* __restrict__ src, int W, int H, uint2* __restrict__ dst, int dw, int dh, float maxColor, float threshold)
+{
+    using namespace bloomk;
+    const int x = (int)blockIdx.x * TILE + ((int)threadIdx.x & (TILE - 1)), y = (int)blockIdx.y * TILE + ((int)threadIdx.x >> 4);
+    if (x >= dw || y >= dh) return;
+    const DevFloatImage f = {src, W, H};
     dst[(size_t)y * (size_t)dw + (size_t)x] = pack_half4(bloomt::down_texel(f, W, H, x, y, dw, dh, true, maxColor, threshold));
 }
 

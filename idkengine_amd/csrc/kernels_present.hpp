@@ -20,7 +20,14 @@
 // Thread shape: one thread per four horizontally adjacent pixels of a row — four 16-B loads, one 16-B store of four RGBA8 texels, so a wave writes 1 KB of contiguous
 // bytes per row; the last W mod 4 pixels of a row are stored texel by texel.  Rows of a width that is no multiple of 4 start at 4-byte multiples only: the 16-B store
 // goes through a 4-byte-aligned vector type.  The RGBA32F format stores four float4.  No LDS, no scratch.
+//
+// k_present_scaled: the same pass when the presentation size differs from the render size (idkptSetPresentationSize; Application.SetResolutions sizes TonemapAndGamma with
+// the presentation resolution, PathTracer with the render resolution).  One invocation per PRESENTATION texel, as the shader's dispatch: uv = (texel + 0.5) / presentation
+// size per axis in binary32, Sampler0 = texture(Result, uv) through the linear, clamp-to-edge filter — bloomt::sample_linear (bloom_texel.hpp), the one filter of the display
+// chain, with a float4 fetch — BEFORE AgX, sRGB and dither; Sampler1 / Sampler2 have the presentation size (a texel fetch, as above); the dither is indexed by the
+// presentation texel.  Same thread shape and stores.  At scales <= 1 the four texels of a thread and its neighbours share taps: the source is read about once through L1 / L2.
 #pragma once
+#include "bloom_texel.hpp"
 
 namespace presentk {
 
@@ -123,16 +130,38 @@ DEV uint32_t quantise(float4 v)
     const uint32_t r = (uint32_t)rintf(gmin(gmax(v.x, 0.0f), 1.0f) * 255.0f), g = (uint32_t)rintf(gmin(gmax(v.y, 0.0f), 1.0f) * 255.0f), b = (uint32_t)rintf(gmin(gmax(v.z, 0.0f), 1.0f) * 255.0f);
     return r | (g << 8) | (b << 16) | 0xff000000u;
 }
-DEV f3 fetch_sum(const float4* s0, const float4* s1, const float4* s2, size_t i)
+// ((0 + a) + s1[i]) + s2[i]: the shader's sum once Sampler0's value a is known
+DEV f3 sum_samplers(f3 a, const float4* s1, const float4* s2, size_t i)
 {
-    const float4 a = s0[i];
     f3 h = mk3(0.0f + a.x, 0.0f + a.y, 0.0f + a.z);
     if (s1) { const float4 b = s1[i]; h = mk3(h.x + b.x, h.y + b.y, h.z + b.z); } else h = mk3(h.x + 0.0f, h.y + 0.0f, h.z + 0.0f);
     if (s2) { const float4 b = s2[i]; h = mk3(h.x + b.x, h.y + b.y, h.z + b.z); } else h = mk3(h.x + 0.0f, h.y + 0.0f, h.z + 0.0f);
     return h;
 }
-
+DEV f3 fetch_sum(const float4* s0, const float4* s1, const float4* s2, size_t i)
+{
+    const float4 a = s0[i];
+    return sum_samplers(mk3(a.x, a.y, a.z), s1, s2, i);
+}
 typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));   // four RGBA8 texels of a row that starts at any texel of the buffer
+// four RGBA8 texels (n == 4: one 16-byte store) or the n < 4 of a row's tail, or n float4
+template <bool F32>
+DEV void store_texels(void* out, size_t base, const float4 v[4], int n)
+{
+    if (F32) {
+        float4* o = (float4*)out + base;
+#pragma unroll
+        for (int k = 0; k < 4; k++) if (k < n) o[k] = v[k];
+    } else {
+        uint32_t* o = (uint32_t*)out + base;
+        if (n == 4) { u32x4_a4 q; q.x = quantise(v[0]); q.y = quantise(v[1]); q.z = quantise(v[2]); q.w = quantise(v[3]); *(u32x4_a4*)o = q; }
+        else {
+#pragma unroll
+            for (int k = 0; k < 3; k++) if (k < n) o[k] = quantise(v[k]);
+        }
+    }
+}
+
 
 }  // namespace presentk
 
@@ -152,16 +181,27 @@ __global__ __launch_bounds__(256) void k_present(const float4* __restrict__ s0, 
     float4 v[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) if (k < n) v[k] = present_texel(fetch_sum(s0, s1, s2, base + k), x0 + k, y, p);
-    if (F32) {
-        float4* o = (float4*)out + base;
+    store_texels<F32>(out, base, v, n);
+}
+
+// Thread t: row t / quads of the presentation image (p.W x p.rows texels), texels 4 (t % quads) ... + 3 of it.  s0 is the W x H image of the render size; s1 / s2 have the presentation size.
+template <bool F32>
+__global__ __launch_bounds__(256) void k_present_scaled(const float4* __restrict__ s0, int W, int H, const float4* __restrict__ s1, const float4* __restrict__ s2, void* __restrict__ out, presentk::Params p)
+{
+    using namespace presentk;
+    const uint32_t quads = ((uint32_t)p.W + 3u) >> 2;
+    const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+    if (t >= quads * (uint32_t)p.rows) return;
+    const int y = (int)(t / quads), x0 = (int)(t - (uint32_t)y * quads) * 4;
+    const size_t base = (size_t)y * (size_t)p.W + (size_t)x0;
+    const int n = min(4, p.W - x0);
+    const bloomk::DevFloatImage src = {s0, W, H};
+    const float v_ = bloomt::texel_coord(y, p.rows);
+    float4 v[4];
 #pragma unroll
-        for (int k = 0; k < 4; k++) if (k < n) o[k] = v[k];
-    } else {
-        uint32_t* o = (uint32_t*)out + base;
-        if (n == 4) { u32x4_a4 q; q.x = quantise(v[0]); q.y = quantise(v[1]); q.z = quantise(v[2]); q.w = quantise(v[3]); *(u32x4_a4*)o = q; }
-        else {
-#pragma unroll
-            for (int k = 0; k < 3; k++) if (k < n) o[k] = quantise(v[k]);
-        }
+    for (int k = 0; k < 4; k++) if (k < n) {
+        const bloomt::V3 a = bloomt::sample_linear(src, bloomt::texel_coord(x0 + k, p.W), v_, W, H, 0, 0);
+        v[k] = present_texel(sum_samplers(mk3(a.x, a.y, a.z), s1, s2, base + k), x0 + k, y, p);
     }
+    store_texels<F32>(out, base, v, n);
 }

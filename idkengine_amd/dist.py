@@ -255,7 +255,14 @@ class GpuShardRenderer:
 
     def local_display(self, settings=None, image=0):
         """idkptPresent (RGBA8) of this rank's rows of the current frame as a (rows, W, 4) uint8 tensor aliasing the library's display buffer; the dither uses the rows'
-        numbers in the whole image, so the gathered display equals the one-GPU display bit for bit."""
+        numbers in the whole image, so the gathered display equals the one-GPU display bit for bit.  The gather deals in rows of the render size: with a presentation
+        size other than it (idkptSetPresentationSize) a rank that holds a shard gets the library's refusal from idkptPresent, and a rank that holds the whole frame (whose
+        present would succeed at the other size) is refused here with the same kind of error."""
+        if self.pt.presentation_size != (self.width, self.height):
+            from ._lib import IdkPtError
+            if self.rows == self.height:
+                raise IdkPtError(f"local_display: the presentation size {self.pt.presentation_size} differs from the render size {(self.width, self.height)} (idkptSetPresentationSize); "
+                                 "the display rows of the ranks are gathered at the render size only")
         ptr, nbytes = self.pt.present_device_ptr(settings, image)
         assert nbytes == self.rows * self.width * 4
         return torch.as_tensor(_DevArray(ptr, (self.rows, self.width, 4), "|u1"), device=self.device)

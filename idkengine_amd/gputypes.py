@@ -176,6 +176,7 @@ class TonemapSettings(C.Structure):
 
 
 IDKPT_DISPLAY_RGBA8, IDKPT_DISPLAY_RGBA32F = 0, 1
+IDKPT_BLOOM_ROUTE_TILED, IDKPT_BLOOM_ROUTE_DIRECT = 0, 1   # enum idkpt_bloom_route (idkptGetBloomRoute): how down pass 0 read the image
 
 
 class BloomSettings(C.Structure):

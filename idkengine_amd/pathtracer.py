@@ -131,6 +131,23 @@ class PathTracer:
         self.width, self.height = width, height
         self._check(self._L.idkptSetSize(self._ctx, width, height))
 
+    def SetPresentationSize(self, width, height):     # Application.SetResolutions(renderRes, presentRes), Application.cs:570-586
+        """idkptSetPresentationSize: the size of the display image (Present) and of bloom's chain and expanded image (Bloom); (0, 0) = the render size, the default.  Kept by
+        SetSize; touches neither the images nor the accumulation.  While it differs from the render size Present and Bloom need one device that holds the whole frame."""
+        self._check(self._L.idkptSetPresentationSize(self._ctx, int(width), int(height)))
+
+    @property
+    def presentation_size(self):
+        """idkptGetPresentationSize: the effective (width, height) — the render size while none is set"""
+        w, h = C.c_int32(), C.c_int32()
+        self._check(self._L.idkptGetPresentationSize(self._ctx, C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    def _display_shape(self):
+        """(rows, width) of the display image: the presentation size where it differs from the render size (whole frame), this context's rows otherwise"""
+        pw, ph = self.presentation_size
+        return (ph, pw) if (pw, ph) != (self.width, self.height) else (self.rows, self.width)
+
     def SetSampleSequence(self, first, stride):
         """Sample-parallel rendering (idkptSetSampleSequence): this context renders the reference's samples first, first + stride, ..."""
         self._check(self._L.idkptSetSampleSequence(self._ctx, int(first), int(stride)))
@@ -453,12 +470,12 @@ class PathTracer:
 
     def Present(self, settings=None, image=0, slot=None, fmt="rgba8", bloom=None):
         """TonemapAndGamma.Compute(PathTracer.Result) + the download of its R8G8B8A8Unorm result: the tone-mapped, sRGB-encoded, dithered image of `image` (0-2) of ring
-        slot `slot` (None: the current one) as an (H, W, 4) numpy array — uint8 for fmt "rgba8", float32 (the value before quantisation) for "rgba32f".  settings: a
+        slot `slot` (None: the current one) as an (H, W, 4) numpy array of the presentation size (SetPresentationSize; the render size by default) — uint8 for fmt "rgba8", float32 (the value before quantisation) for "rgba32f".  settings: a
         gputypes.TonemapSettings; None = the reference's defaults with DoTonemapAndSrgbTransform = not DoDebugBVHTraversal, as Application.cs:222 sets it.
         bloom: None = no bloom (an unbound Sampler1); a gputypes.BloomSettings (or True: the reference's defaults) runs idkptBloom on the same image first and adds its
         expanded image as the shader's Sampler1, all on the device (one device, whole frame only)."""
         slot, f = self._present(settings, image, slot, fmt, bloom)
-        out = np.zeros((self.rows, self.width, 4), np.float32 if f == T.IDKPT_DISPLAY_RGBA32F else np.uint8)
+        out = np.zeros(self._display_shape() + (4,), np.float32 if f == T.IDKPT_DISPLAY_RGBA32F else np.uint8)
         self._check(self._L.idkptDownloadDisplay(self._ctx, slot, out.ctypes.data, out.nbytes))
         return out
 
@@ -484,9 +501,10 @@ class PathTracer:
 
     def Bloom(self, settings=None, image=0, slot=None):
         """Bloom.Compute(image `image` (0-2) of ring slot `slot`; None: the current one) and what the tonemap shader reads of its result: the up chain's level 0 magnified to
-        the frame, an (H, W, 4) float32 array (rgb, 1.0).  settings: a gputypes.BloomSettings; None = the reference's defaults (1.5, 3.8, MinusLods 3)."""
+        the frame, an (H, W, 4) float32 array (rgb, 1.0) of the presentation size.  settings: a gputypes.BloomSettings; None = the reference's defaults (1.5, 3.8, MinusLods 3)."""
         p, n = self.bloom_device_ptr(settings, image, slot)
-        out = np.zeros((self.height, self.width, 4), np.float32)
+        pw, ph = self.presentation_size
+        out = np.zeros((ph, pw, 4), np.float32)
         if n != out.nbytes:
             raise IdkPtError(f"Bloom: the expanded image has {n} bytes, expected {out.nbytes} (height * width * 16)")
         self.read_device(p, out)
@@ -513,6 +531,18 @@ class PathTracer:
         lv, w0, h0 = C.c_int32(), C.c_int32(), C.c_int32()
         self._check(self._L.idkptGetBloomInfo(self._ctx, -1 if slot is None else int(slot), C.byref(lv), C.byref(w0), C.byref(h0)))
         return lv.value, w0.value, h0.value
+
+    def bloom_chain_device_ptr(self, chain, slot=None):
+        """idkptGetBloomChainDevicePtr: (device pointer, bytes) of the whole down (chain 0) or up (chain 1) chain of the slot's last bloom, level 0 first; 64 guard bytes follow"""
+        p = C.c_void_p(); n = C.c_size_t()
+        self._check(self._L.idkptGetBloomChainDevicePtr(self._ctx, -1 if slot is None else int(slot), int(chain), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def bloom_route(self, slot=None):
+        """idkptGetBloomRoute of the slot's last bloom: gputypes.IDKPT_BLOOM_ROUTE_TILED or IDKPT_BLOOM_ROUTE_DIRECT (how down pass 0 read the image)"""
+        r = C.c_int32()
+        self._check(self._L.idkptGetBloomRoute(self._ctx, -1 if slot is None else int(slot), C.byref(r)))
+        return r.value
 
     def bloom_level(self, chain, level, slot=None):
         """idkptDownloadBloom: level `level` of the down (chain 0) or up (chain 1) chain of the slot's last bloom, an (h, w, 4) float16 array (the stored RGBA16F bits)."""

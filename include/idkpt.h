@@ -197,10 +197,11 @@ typedef struct idkpt_stats {
 } idkpt_stats;
 /* The layout above only ever GROWS at its end, and IDKPT_ABI_VERSION counts the growths (and every other change a host compiled against an older header could trip over: new
  * enum values of idkpt_buffer or idkpt_texture_format, new fields of idkpt_texture, new entry points: 5 = idkptComputeSky / idkptUpdateSky / idkptDownloadSky, 6 = idkptPresent / idkptDownloadDisplay / idkptGetDisplayDevicePtr,
- * 7 = idkptBloom / idkptGetBloomInfo / idkptDownloadBloom / idkptGetBloomDevicePtr, 8 = idkptUnprojectSky).  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
+ * 7 = idkptBloom / idkptGetBloomInfo / idkptDownloadBloom / idkptGetBloomDevicePtr, 8 = idkptUnprojectSky,
+ * 9 = idkptSetPresentationSize / idkptGetPresentationSize / idkptGetBloomRoute / idkptGetBloomChainDevicePtr).  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
  * of ITS struct to idkptGetStatsSized and gets exactly that many bytes; idkptGetStats(ctx, out) is idkptGetStatsSized(ctx, out, sizeof(idkpt_stats)) of the header the LIBRARY
  * was built with — for hosts built from the same tree.  idkptGetAbiVersion() lets a host refuse a library older than the header it was written against. */
-#define IDKPT_ABI_VERSION 8
+#define IDKPT_ABI_VERSION 9
 
 /* ---- lifetime --------------------------------------------------------------------------- */
 /* new PathTracer(w,h,settings) (PathTracer.cs:170-212).  deviceCount = 1: the reference's situation, one GPU.
@@ -452,7 +453,7 @@ IDKPT_API int32_t idkptGetFrameDevicePtr(idkpt_ctx* ctx, int32_t slot, int32_t i
 /* ---- display output (ABI 6): TonemapAndGammaCorrect.Compute (Source/Render/TonemapAndGammaCorrecter.cs, Shaders/TonemapAndGammaCorrect/compute.glsl) -------------------
  * The one pass between PathTracer.Result and the swapchain (Source/Application.cs:217-223): AgX tonemap, sRGB transfer and the 8 x 8 Bayer dither, run on the device so
  * that a displayed frame leaves it as 4 bytes per pixel instead of 16.  The shader's Sampler1 / Sampler2 are device pointers (dAdd0 / dAdd1): idkptBloom below fills
- * Sampler1 as the engine does.  Resampling to another presentation size stays with the host: the display image has the render size. */
+ * Sampler1 as the engine does.  The display image has the presentation size (idkptSetPresentationSize below), which is the render size by default. */
 typedef struct idkpt_tonemap { float Exposure, Saturation, Linear, Peak, Compression; int32_t DoTonemapAndSrgbTransform; } idkpt_tonemap;
 /* TonemapAndGammaCorrect.GpuSettings, same order; the reference's defaults 0.45, 1.06, 0.18, 1.0, 0.1, 1.  DoTonemapAndSrgbTransform = 0 is the reference's
  * DoDebugBVHTraversal path (Application.cs:222): clamp to [0, 1], no sRGB, dither. */
@@ -500,7 +501,7 @@ IDKPT_API int32_t idkptGetDisplayDevicePtr(idkpt_ctx* ctx, int32_t slot, void** 
  * belong to a ring slot (the down chain, the up chain, the expanded image), are allocated at the slot's first bloom, re-made by idkptSetSize / idkptSetFrameRing and the
  * row layout calls, kept by idkptSetMaxBatch, and each ends with 64 guard bytes of value 0xA5 that nothing writes; a context that never blooms allocates nothing.
  * Validated before anything is launched: slot (-1: the current slot) and image in range, Threshold and MaxColor finite, MinusLods >= 0 (IDKPT_ERR_INVALID_ARGUMENT);
- * no size set, width < 2 or height < 2, a shard of the rows (IDKPT_ERR_INVALID_OPERATION). */
+ * no size set, width < 2 or height < 2 (of the presentation size), a shard of the rows (IDKPT_ERR_INVALID_OPERATION). */
 typedef struct idkpt_bloom { float Threshold, MaxColor; int32_t MinusLods; } idkpt_bloom;   /* Bloom.GpuSettings + MinusLods; the reference's defaults 1.5, 3.8, 3 */
 IDKPT_API int32_t idkptBloom(idkpt_ctx* ctx, int32_t slot, int32_t image, const idkpt_bloom* bloom);   /* Bloom.Compute(image `image` of slot `slot`) */
 /* The last bloom of a slot (-1: the current slot); IDKPT_ERR_INVALID_OPERATION if the slot was not bloomed since the last resize.  Out pointers may be NULL.
@@ -510,6 +511,40 @@ IDKPT_API int32_t idkptBloom(idkpt_ctx* ctx, int32_t slot, int32_t image, const 
 IDKPT_API int32_t idkptGetBloomInfo(idkpt_ctx* ctx, int32_t slot, int32_t* levels, int32_t* w0, int32_t* h0);
 IDKPT_API int32_t idkptDownloadBloom(idkpt_ctx* ctx, int32_t slot, int32_t chain, int32_t level, void* dst, size_t bytes);
 IDKPT_API int32_t idkptGetBloomDevicePtr(idkpt_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes);
+
+/* ---- presentation size (ABI 9): Application.SetResolutions(renderRes, presentRes) (Source/Application.cs:570-586) ------------------------------------------------------
+ * The engine sizes PathTracer with the RENDER resolution and Bloom and TonemapAndGamma with the PRESENTATION resolution; renderRes = presentRes * RenderResolutionScale, the
+ * GUI's slider from 0.1 to 1.0.  With a scale below 1, Bloom.Compute builds a chain of presentRes / 2 and below whose first pass reads the smaller Result through a linear,
+ * clamp-to-edge sampler, and TonemapAndGamma.Compute runs one invocation per presentation texel: texture(Sampler0, uv) magnifies the HDR Result bilinearly BEFORE AgX, sRGB
+ * and the dither, and the dither is indexed by the presentation texel.  A host cannot get that picture by resampling the RGBA8 display image (that filters behind the tone
+ * curve and smears the dither pattern).
+ *   idkptSetPresentationSize(ctx, width, height)    the size of the display image and of bloom's chain and expanded image; (0, 0) = the render size (the default)
+ *   idkptGetPresentationSize(ctx, &width, &height)  the effective size (the render size while none is set); out pointers may be NULL
+ * The presentation size is a state of its own: idkptSetSize, idkptSetFrameRing and idkptSetMaxBatch keep it.  Setting it releases the display and bloom buffers (re-made at
+ * their next use, as after idkptSetSize) and touches NEITHER the images NOR the accumulation: nothing queued is launched, idkptGetAccumulatedSamples is unchanged, a window
+ * resize at a fixed render size keeps accumulating.  Negative sizes, sizes beyond 65536, or exactly one zero: IDKPT_ERR_INVALID_ARGUMENT.
+ * While the effective presentation size EQUALS the render size — none set, or the same numbers set — idkptPresent and idkptBloom run exactly the kernels they ran before this
+ * call existed: nothing changes by a bit.  When it DIFFERS:
+ *   idkptPresent   one invocation per presentation texel: uv = (texel + 0.5) / presentation size per axis in binary32; Sampler0 = the slot's image (render size) through the
+ *                  linear, clamp-to-edge filter of the bloom section above (f = u * size - 0.5, floor, fractional weights, clamped indices, mix(x, y, a) = x (1 - a) + y a);
+ *                  the sum ((0 + s0) + s1) + s2, AgX, sRGB, and the dither BayerMatrix8[x % 8][y % 8] of the PRESENTATION texel.  dAdd0 / dAdd1 are RGBA32F images of the
+ *                  presentation size (height * width texels), fetched per texel.  The display buffer, idkptDownloadDisplay and idkptGetDisplayDevicePtr have
+ *                  presentation height * width texels; guard bytes and validation as above.
+ *   idkptBloom     `levels`, w0 and h0 come from the presentation size (Bloom.SetSize(presentRes)); down pass 0 reads the render-size image through the same filter with uv
+ *                  of the written level; every later pass is unchanged; the expanded image has the presentation size (idkptGetBloomDevicePtr: height * width * 16 bytes)
+ *                  and stays the engine's Sampler1 when passed as dAdd0.  The presentation size must be at least 2 x 2; the render size may be anything idkptSetSize takes,
+ *                  also LARGER than the presentation size (supersampling): down pass 0 then fetches its taps from memory instead of staging tiles (idkptGetBloomRoute).
+ * The scaled path works on ONE device that holds the WHOLE frame, as idkptBloom always did (a shard would need halo rows): a multi-device context, and a context that holds
+ * row bands or a strip, get IDKPT_ERR_INVALID_OPERATION from idkptPresent and idkptBloom while the sizes differ, before anything is launched. */
+IDKPT_API int32_t idkptSetPresentationSize(idkpt_ctx* ctx, int32_t width, int32_t height);
+IDKPT_API int32_t idkptGetPresentationSize(idkpt_ctx* ctx, int32_t* outWidth, int32_t* outHeight);
+/* How down pass 0 of the slot's last bloom read the image (an observation for tests and profiles; both routes compute the same texels bit for bit).  Errors as idkptGetBloomInfo. */
+enum idkpt_bloom_route { IDKPT_BLOOM_ROUTE_TILED = 0 /* source tiles staged in LDS */, IDKPT_BLOOM_ROUTE_DIRECT = 1 /* clamped fetches from memory: a tile's taps span more than it stages */ };
+IDKPT_API int32_t idkptGetBloomRoute(idkpt_ctx* ctx, int32_t slot, int32_t* outRoute);
+/* A whole chain of the slot's last bloom as it lies in device memory (chain 0 = down, 1 = up): its levels one behind the other, level 0 first, 8 bytes per texel; *outBytes
+ * is their sum, and the chain's 64 guard bytes of 0xA5 follow directly behind.  For hosts that sample a level themselves and for tests that look at the guard; does not wait:
+ * valid in stream order (idkptGetStream) until the next bloom of that slot or resize.  Errors as idkptGetBloomDevicePtr; a wrong chain: IDKPT_ERR_INVALID_ARGUMENT. */
+IDKPT_API int32_t idkptGetBloomChainDevicePtr(idkpt_ctx* ctx, int32_t slot, int32_t chain, void** outPtr, size_t* outBytes);
 
 /* ---- render ----------------------------------------------------------------------------- */
 /* PathTracer.ResetAccumulation (PathTracer.cs:334-337) */
