@@ -28,6 +28,9 @@ static int alloc_frame_impl(dev_ctx* ctx)
     ctx->countersDirty = true;   // (the first batch resets its counters itself)
     HIPC(hipMemsetAsync(ctx->aovA.p, 0, cap * 16, ctx->stream)); HIPC(hipMemsetAsync(ctx->aovN.p, 0, cap * 16, ctx->stream));
     HIPC(hipMemsetAsync(ctx->contFlag.p, 0, cap, ctx->stream));   // per-batch values are written by k_gen_primary; the pad ids [N, Npad) must read 0
+    // Invariant between batches: NO byte has bit 0 ("continues") set.  k_shade_first / k_trace_fused set it, k_scan_local<true> of the same batch consumes and clears it.  That lets
+    // a pixel-major batch leave the bytes of its sky-classified tiles unwritten: whatever they hold from an earlier batch (0, 2, 4) cannot enqueue a ray, and whether such a
+    // pixel is "culled per tile" is read from the batch's tile classes, which take precedence over the byte (k_regen_culled).
     ctx->accum.assign(ctx->ringSize, 0u); ctx->curSlot = 0; ctx->ringStarted = false;
     for (DevBuf& b : ctx->disp) b.release();                       // display images (idkptPresent) belong to a frame size and a ring: re-made at their next use
     ctx->disp.clear(); ctx->dispFmt.clear();

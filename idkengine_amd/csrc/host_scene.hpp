@@ -368,8 +368,8 @@ static int tex_descs_upload(dev_ctx* ctx)
     return IDKPT_OK;
 }
 
-// The fast path stores nothing but a flag for pre-culled pixels of the most recent sample; this completes their ray state (origin,
-// direction, miss radiance) from the frame constants of that batch.  Must run while the scene the batch was rendered with is still
+// The fast path stores nothing but a flag for pre-culled pixels of the most recent sample — for the tiles classified as sky not even that: their class, which stays in
+// ctx->tileClass until the next batch is launched, says so; this completes their ray state (origin, direction, miss radiance) from the frame constants of that batch.  Must run while the scene the batch was rendered with is still
 // resident (the sky decides the miss radiance): called by idkptDownloadRays and before a new scene replaces the old one.
 static DScene make_dscene_last(dev_ctx* ctx);
 static int materialize_culled_rays(dev_ctx* ctx)
@@ -377,7 +377,7 @@ static int materialize_culled_rays(dev_ctx* ctx)
     if (!ctx->lastNeedsRegen) return IDKPT_OK;
     const size_t N = (size_t)ctx->W * ctx->rows;
     RayBufs rays = {ctx->rayO.as<float4>(), ctx->rayT.as<float4>(), ctx->rayR.as<float4>(), ctx->aovA.as<float4>(), ctx->aovN.as<float4>()};
-    hipLaunchKernelGGL(k_regen_culled, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, make_dscene_last(ctx), ctx->lastFrame, rays, (const uint8_t*)ctx->contFlag.as<uint8_t>(), (uint32_t)(ctx->lastBatch - 1), (uint32_t)N);
+    hipLaunchKernelGGL(k_regen_culled, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, make_dscene_last(ctx), ctx->lastFrame, rays, (const uint8_t*)ctx->contFlag.as<uint8_t>(), ctx->lastTileClass ? (const uint8_t*)ctx->tileClass.as<uint8_t>() : (const uint8_t*)nullptr, (uint32_t)(ctx->lastBatch - 1), (uint32_t)N);
     HIPC(hipGetLastError());
     ctx->lastNeedsRegen = false;
     return IDKPT_OK;
@@ -636,7 +636,7 @@ static int32_t dev_DownloadTexture(dev_ctx* ctx, int32_t index, int32_t* outResi
 // 1-6 and 8 and the deferred bounce leave radiance that is only produced on demand, from the sky — are completed while the OLD sky is resident.  The new sky is then enqueued
 // on the context's stream, behind all of that; nothing waits for the stream, except once when S outgrows the allocation (the old one is released: as dev_BuildTlas does).
 // The tile classes depend on skySize (kernels_trace.hpp k_classify_tiles: 7 no sky, 8 textured, 1-6 constant faces); they are derived anew for every batch from the DScene
-// of that batch, and the one consumer that outlives a batch (k_regen_culled: contFlag + lastFrame) has just run — no classification survives this call.
+// of that batch, and the one consumer that outlives a batch (k_regen_culled: contFlag + tileClass + lastFrame) has just run — no classification survives this call.
 static int sky_begin(dev_ctx* ctx, int32_t S)
 {
     HIPC(hipSetDevice(ctx->device));

@@ -60,12 +60,18 @@ __global__ __launch_bounds__(256) void k_final_draw(DScene s, Frame f, RayBufs r
 }
 
 // idkptDownloadRays support: the ray-state planes k_gen_primary skipped for culled pixels (flag 2) of one sample of the batch
-__global__ __launch_bounds__(256) void k_regen_culled(DScene s, Frame f, RayBufs rays, const uint8_t* contFlag, uint32_t smp, uint32_t N)
+// tileClass (null: the batch had none): a pixel of a classified tile is "culled per tile" whatever its byte holds — pixel-major batches store no byte for those tiles, and
+// what an earlier batch left there (0, 2 or 4; never bit 0, k_scan_local) says nothing about this one
+__global__ __launch_bounds__(256) void k_regen_culled(DScene s, Frame f, RayBufs rays, const uint8_t* contFlag, const uint8_t* tileClass, uint32_t smp, uint32_t N)
 {
     const uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= N) return;
     const size_t rid = (size_t)smp * f.Npad + pix;
-    const uint8_t flag = contFlag[rid];
+    uint8_t flag = contFlag[rid];
+    if (tileClass) {
+        const uint32_t px = pix % (uint32_t)f.W, py = pix / (uint32_t)f.W, tilesX = ((uint32_t)f.W + 7) / 8, nTilesAll = tilesX * (((uint32_t)f.rows + 7) / 8);
+        if (tileClass[(f.tilePerSample ? (size_t)smp * nTilesAll : 0) + (py >> 3) * tilesX + (px >> 3)] != 0u) flag = 4;
+    }
     if (flag != 2 && flag != 4) return;                                 // 2: culled per pixel, 4: culled per tile (no ray was generated at all); bit 0 = continues
     f3 origin; f2 pd; uint32_t seed;
     gen_primary(f, smp, pix, sample_index(f, smp), origin, pd, seed);

@@ -39,7 +39,7 @@ __global__ __launch_bounds__(256) void k_band_starts(const uint32_t* queue, cons
 // (3) scatter (k_compact).
 #define SCAN_WAVES_PER_BLOCK 256
 template <bool FROM_FLAGS>
-__global__ __launch_bounds__(SCAN_WAVES_PER_BLOCK) void k_scan_local(const uint32_t* countPtr, uint32_t countImm, const uint8_t* contFlag, unsigned long long* contMask, uint32_t* waveLocal, uint32_t* blockSums)
+__global__ __launch_bounds__(SCAN_WAVES_PER_BLOCK) void k_scan_local(const uint32_t* countPtr, uint32_t countImm, uint8_t* contFlag, unsigned long long* contMask, uint32_t* waveLocal, uint32_t* blockSums)
 {
     __shared__ uint32_t part[SCAN_WAVES_PER_BLOCK];
     const uint32_t N = countPtr ? *countPtr : countImm;
@@ -50,11 +50,15 @@ __global__ __launch_bounds__(SCAN_WAVES_PER_BLOCK) void k_scan_local(const uint3
     if (w < nW) {
         unsigned long long m;
         if (FROM_FLAGS) {
-            const uint4* p = reinterpret_cast<const uint4*>(contFlag + (size_t)w * 64);
+            // The "continues" bits (bit 0 of a ray's byte, set by k_shade_first / k_trace_fused) are consumed here and cleared again: between batches no byte has bit 0 set,
+            // so a slot this batch does not write at all (a tile classified as sky, kernels_trace.hpp k_gen_primary) cannot enqueue a ray that continued in an earlier batch.
+            // Bits 1 and 2 (culled per pixel / per tile) stay for k_regen_culled.
+            uint4* p = reinterpret_cast<uint4*>(contFlag + (size_t)w * 64);
             m = 0ull;
             for (int q = 0; q < 4; q++) {
                 uint4 v = p[q]; uint32_t d[4] = {v.x, v.y, v.z, v.w};
                 for (int k = 0; k < 4; k++) for (int bb = 0; bb < 4; bb++) m |= (unsigned long long)((d[k] >> (8 * bb)) & 1u) << (q * 16 + k * 4 + bb);
+                if ((v.x | v.y | v.z | v.w) & 0x01010101u) p[q] = make_uint4(v.x & 0xfefefefeu, v.y & 0xfefefefeu, v.z & 0xfefefefeu, v.w & 0xfefefefeu);
             }
             contMask[w] = m;
         } else m = contMask[w];

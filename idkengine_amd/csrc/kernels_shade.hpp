@@ -36,7 +36,9 @@ __global__ __launch_bounds__(256) void k_shade_first(DScene s0, Frame f, RayBufs
 {
     __shared__ uint32_t waveCont[4]; __shared__ uint32_t blockBase;
     const uint32_t item = blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = item < *activeCount;
+    const uint32_t nActive = *activeCount;
+    if (blockIdx.x * blockDim.x >= nActive) return;       // block-uniform, before the first barrier: the grid covers every slot of the batch, the list only the rays that traverse
+    const bool live = item < nActive;
     if (!pmList && !live) return;
     bool cont = false; uint32_t rid = 0;
     if (live) {

@@ -177,6 +177,10 @@ __global__ __launch_bounds__(1024) void k_gen_primary(DScene s0, Frame f, RayBuf
     // groups: 32 samples = 2 x 16, the driver's 20 = 2 x 10), and it appends its survivors pixel by pixel (all samples of a pixel side by side): a wave of the traversal kernel then
     // holds 64 / G pixels x G samples, rays that differ by their sub-pixel jitter only
     const bool pm = f.genPixelMajor != 0;
+    // pixel-major batches share ONE classification (host: never with per-sample cameras or scene versions), and a workgroup is one tile: in a tile classified as sky it has
+    // nothing to do at all.  No flag byte is stored: every consumer of "culled per tile" takes it from the tile class (k_final_draw, k_regen_culled), and the slots' stale bytes
+    // never have bit 0 set (k_scan_local<true> clears the bits it consumes — the invariant stated at the allocation, host_frame.hpp)
+    if (pm && tileClass && blockIdx.y < ((uint32_t)f.W + 7) / 8 * (((uint32_t)f.rows + 7) / 8) && tileClass[blockIdx.y] != 0u) return;
     const uint32_t G = blockDim.x >> 6;                                 // pixel-major: samples (= waves) of this workgroup
     const uint32_t smp = pm ? blockIdx.x * G + (threadIdx.x >> 6) : blockIdx.x;   // sample of the batch
     const DScene s = VER ? scene_of_sample(s0, min(smp, (uint32_t)f.batch - 1u)) : s0;   // (wave-uniform)
@@ -258,8 +262,7 @@ __global__ __launch_bounds__(1024) void k_gen_primary(DScene s0, Frame f, RayBuf
     const unsigned long long m = __ballot(keep);
     const uint32_t wv = threadIdx.x >> 6;
     if (pm) {
-        if (cls != 0u) return;                               // (a tile classified as sky — pixel-major batches share one classification: workgroup-uniform, nothing to append)
-        if (lane == 0) keepMask[wv] = m;
+        if (lane == 0) keepMask[wv] = m;                     // (a tile classified as sky never gets here: its workgroup returned at the top)
         __syncthreads();
         uint32_t cnt = 0, before = 0;                       // samples of this workgroup that keep pixel `lane`; those of them in waves before this one
         for (uint32_t w = 0; w < G; w++) { const uint32_t b = (uint32_t)(keepMask[w] >> lane) & 1u; cnt += b; before += w < wv ? b : 0u; }
