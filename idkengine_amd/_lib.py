@@ -13,7 +13,7 @@ SYMBOLS = [
     "idkptSetPerFrame", "idkptSetPerFrameData", "idkptUploadScene", "idkptUpdateBuffer", "idkptUpdateTexture", "idkptDownloadTexture", "idkptComputeSky", "idkptUpdateSky", "idkptUnprojectSky", "idkptDownloadSky", "idkptSetLightCount",
     "idkptBuildTlas", "idkptBuildTlasOnDevice", "idkptBuildBlasCore", "idkptBuildBlas", "idkptBuildBlasFetch", "idkptCbrtProbe", "idkptRefitBlas", "idkptUploadUnskinnedVertices", "idkptSkin", "idkptDownloadBuffer",
     "idkptResetAccumulation", "idkptGetAccumulatedSamples", "idkptSetSampleSequence", "idkptRender", "idkptSynchronize", "idkptDownload",
-    "idkptDownloadRays", "idkptDownloadAliveQueue", "idkptEnablePrimaryHitCapture", "idkptDownloadPrimaryHits",
+    "idkptDownloadRays", "idkptDownloadAliveQueue", "idkptEnablePrimaryHitCapture", "idkptDownloadPrimaryHits", "idkptDownloadTileClasses",
     "idkptGetStats", "idkptGetStatsSized", "idkptResetStats", "idkptEnableCounters", "idkptEnableTiming", "idkptGetImageDevicePtr",
     "idkptSetStream", "idkptGetStream", "idkptSetDeveloperOption", "idkptSetMaxBatch", "idkptFlush", "idkptTraceRays", "idkptTraceShadows", "idkptTraceRaysDevice", "idkptTraceShadowsDevice", "idkptSetFrameRing", "idkptBeginFrame", "idkptDownloadFrame", "idkptGetFrameDevicePtr",
     "idkptPresent", "idkptDownloadDisplay", "idkptGetDisplayDevicePtr",
@@ -52,7 +52,7 @@ def load():
         "idkptDownloadBuffer": [vp, i32, sz, sz, vp], "idkptResetAccumulation": [vp], "idkptSetSampleSequence": [vp, u32, u32], "idkptGetAccumulatedSamples": [vp, C.POINTER(u32)],
         "idkptRender": [vp], "idkptSynchronize": [vp], "idkptDownload": [vp, i32, vp, sz], "idkptDownloadRays": [vp, vp, sz],
         "idkptDownloadAliveQueue": [vp, vp, sz, C.POINTER(u32)], "idkptEnablePrimaryHitCapture": [vp, i32],
-        "idkptDownloadPrimaryHits": [vp, vp, vp, vp, sz], "idkptGetStats": [vp, vp], "idkptGetStatsSized": [vp, vp, sz], "idkptResetStats": [vp],
+        "idkptDownloadPrimaryHits": [vp, vp, vp, vp, sz], "idkptDownloadTileClasses": [vp, vp, sz, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)], "idkptGetStats": [vp, vp], "idkptGetStatsSized": [vp, vp, sz], "idkptResetStats": [vp],
         "idkptEnableCounters": [vp, i32], "idkptEnableTiming": [vp, i32], "idkptGetImageDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(sz)],
         "idkptSetStream": [vp, vp], "idkptGetStream": [vp, C.POINTER(vp)], "idkptSetDeveloperOption": [vp, C.c_char_p, i32], "idkptSetMaxBatch": [vp, i32], "idkptFlush": [vp],
     }

@@ -101,6 +101,24 @@ static int32_t dev_DownloadPrimaryHits(dev_ctx* ctx, float* t, uint32_t* triangl
     return IDKPT_OK;
 }
 
+// test support (idkptDownloadTileClasses): the classes k_classify_tiles gave the 8x8 tiles of the last launched batch, [set][tile]; sets = 0 when that batch had none
+static int32_t dev_DownloadTileClasses(dev_ctx* ctx, uint8_t* out, size_t bytes, int32_t* tilesX, int32_t* tilesY, int32_t* sets)
+{
+    if (!ctx || !tilesX || !tilesY || !sets) return IDKPT_ERR_INVALID_ARGUMENT;
+    HIPC(hipSetDevice(ctx->device));
+    FLUSH_KEEP();
+    const bool have = ctx->lastFast && ctx->lastTileClass;      // (lastFast is cleared with the frame buffers: nothing rendered since a resize)
+    const int32_t tx = have ? (ctx->lastFrame.W + 7) / 8 : 0, ty = have ? (ctx->lastFrame.rows + 7) / 8 : 0;
+    const int32_t n = have ? (ctx->lastFrame.tilePerSample ? ctx->lastBatch : 1) : 0;
+    *tilesX = tx; *tilesY = ty; *sets = n;
+    if (!out) return IDKPT_OK;                           // (the sizes only)
+    const size_t need = (size_t)n * tx * ty;
+    REQUIRE(bytes == need, "idkptDownloadTileClasses: bytes must equal sets*tilesX*tilesY (call with out = NULL for the three numbers)");
+    if (need) { REQUIRE(ctx->tileClass.bytes >= need, "idkptDownloadTileClasses: no classification is resident"); HIPC(hipMemcpyAsync(out, ctx->tileClass.p, need, hipMemcpyDeviceToHost, ctx->stream)); }
+    SYNC_CHECKED();
+    return IDKPT_OK;
+}
+
 static int32_t dev_GetStats(dev_ctx* ctx, idkpt_stats* out)
 {
     if (!ctx || !out) return IDKPT_ERR_INVALID_ARGUMENT;

@@ -953,6 +953,16 @@ int32_t idkptDownloadAliveQueue(idkpt_ctx* c, uint32_t* indices, size_t capacity
     return IDKPT_OK;
 }
 int32_t idkptEnablePrimaryHitCapture(idkpt_ctx* c, int32_t enable) { if (!c) return IDKPT_ERR_INVALID_ARGUMENT; for (dev_ctx* m : c->dev) dev_EnablePrimaryHitCapture(m, enable); return IDKPT_OK; }
+// one device only: of a multi-device context, member 0's tiles (its local rows)
+int32_t idkptDownloadTileClasses(idkpt_ctx* c, uint8_t* out, size_t bytes, int32_t* tilesX, int32_t* tilesY, int32_t* sets)
+{
+    if (!c || !tilesX || !tilesY || !sets) return IDKPT_ERR_INVALID_ARGUMENT;
+    ONE(dev_DownloadTileClasses(m, out, bytes, tilesX, tilesY, sets));
+    GFLUSH();
+    dev_ctx* m = c->dev[0];
+    const int rc = dev_DownloadTileClasses(m, out, bytes, tilesX, tilesY, sets);
+    return rc ? mfail(c, m, rc) : IDKPT_OK;
+}
 int32_t idkptDownloadPrimaryHits(idkpt_ctx* c, float* t, uint32_t* triangleId, float* baryXY, size_t pixelCount)
 {
     if (!c || !t || !triangleId || !baryXY) return IDKPT_ERR_INVALID_ARGUMENT;

@@ -61,8 +61,8 @@ __global__ __launch_bounds__(WAVE) void k_trace_queue(DScene s, Frame f, RayBufs
 // k_classify_tiles: once per batch, one thread per 8x8 tile (sample-independent).  A tile whose whole beam of possible primary rays
 // — every jitter offset, every point of the lens — provably misses the root box, and provably looks at one face of a constant-per-face
 // sky, needs no per-pixel ray generation at all: its pixels are the FirstHit miss branch with a known colour (FirstHit:225-233).
-// The test is CONSERVATIVE (box strictly outside one side plane of the tile's pyramid, by a margin that covers the lens radius, the
-// direction tilt LenseRadius/FocalLength, one extra pixel of jitter and rounding); tiles that fail it take the exact per-pixel path,
+// The test is CONSERVATIVE (box strictly outside one side plane of the tile's pyramid, by a margin that covers the reach R = sqrt(2) * LenseRadius of the lens, the
+// direction tilt R/FocalLength, one extra pixel of jitter and rounding); tiles that fail it take the exact per-pixel path,
 // so results are bit-identical either way.  class 0 = per-pixel path, 1..6 = miss + sky face (class-1), 7 = miss + no sky (black),
 // 8 = miss + a textured sky (an HDR cube map, the engine's default: SkyBoxManager.cs:44,74): k_final_draw generates the pixel's ray and samples the sky itself
 // (the arithmetic of k_gen_primary's miss branch), so nothing is stored per sample for those pixels either.
@@ -78,6 +78,9 @@ __global__ __launch_bounds__(256) void k_classify_tiles(DScene s0, Frame f, uint
     const uint32_t tx = t % tilesX, ty = t / tilesX;
     uint8_t cls = 0;
     const float r = f.g.LenseRadius, F = f.g.FocalLength;
+    // how far a ray origin can lie from the axis: SampleDisk (Sampling.glsl:98-114) returns `point * 2 - 1` of a point of the unit quarter disc, which reaches the corner (-1, -1) —
+    // sqrt(2) radii.  The side planes of a tile see at most r of it while InvProjection is diagonal; a sheared one turns them (tests/adversarial_cameras.py lens_sheared_near)
+    const float R = 1.41422f * r;
     if (s.instanceCount >= 1 && s.instanceCount <= 256 && !f.outputAovs && r >= 0.0f && F > 1e-3f && r / F <= 0.05f) {
         const float W = (float)f.W, H = (float)f.H;
         const int gy0 = global_row(f, (int)(ty * 8)), gy1 = global_row(f, (int)(ty * 8 + 7));   // global rows of the tile's first / last local row (monotone in the local row)
@@ -124,7 +127,7 @@ __global__ __launch_bounds__(256) void k_classify_tiles(DScene s0, Frame f, uint
                 rel[c] = mk3(m0.x * cx + m0.y * cy + m0.z * cz + m0.w, m1.x * cx + m1.y * cy + m1.z * cz + m1.w, m2.x * cx + m2.y * cy + m2.z * cz + m2.w) - C;
                 D = gmax(D, gsqrt(dot(rel[c], rel[c])));
             }
-            const float margin = r + (D + r) * (r / F) * 1.5f + 1e-4f * (D + 1.0f);
+            const float margin = R + (D + R) * (R / F) * 1.5f + 1e-4f * (D + 1.0f);
             bool boxOutside = false;
             for (int i = 0; i < 4; i++) {
                 if (!planeOk[i]) continue;
@@ -139,8 +142,8 @@ __global__ __launch_bounds__(256) void k_classify_tiles(DScene s0, Frame f, uint
             else if (s.skySize > 1) cls = 8;
             else {
                 // one sky face for every direction of the beam: a strictly dominant axis, same sign, at all four corners, by more than
-                // twice the possible tilt (lens + oct-encoding round trip)
-                const float eta = 2.0f * (r / F) + 1e-4f;
+                // twice the possible tilt R / F (lens + oct-encoding round trip)
+                const float eta = 2.0f * (R / F) + 1e-4f;
                 int face = -1; bool same = true;
                 for (int i = 0; i < 4; i++) {
                     const float ax = gabs(u[i].x), ay = gabs(u[i].y), az = gabs(u[i].z);

@@ -390,6 +390,16 @@ class PathTracer:
         self._check(self._L.idkptDownloadPrimaryHits(self._ctx, t.ctypes.data, tri.ctypes.data, bary.ctypes.data, n))
         return t, tri, bary
 
+    def tile_classes(self):
+        """idkptDownloadTileClasses (a diagnostic): the classes of the 8x8 tiles of the last launched batch, a (sets, tilesY, tilesX) uint8 array — 0 per-pixel path, 1-6 proven
+        miss + sky face, 7 proven miss without a sky, 8 proven miss under a textured sky; sets = 0 when that batch ran without a classification.  Member 0 of a multi-device context."""
+        tx, ty, sets = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(self._L.idkptDownloadTileClasses(self._ctx, None, 0, C.byref(tx), C.byref(ty), C.byref(sets)))
+        out = np.zeros((sets.value, ty.value, tx.value), np.uint8)
+        if out.size:
+            self._check(self._L.idkptDownloadTileClasses(self._ctx, out.ctypes.data, out.nbytes, C.byref(tx), C.byref(ty), C.byref(sets)))
+        return out
+
     def UpdateTexture(self, index, image):
         """idkptUpdateTexture: image `index` of the texture table (a float32 array or a gputypes.TextureImage)."""
         t = T.TextureImage.of(image); rec = T.Texture(); t.fill(rec)

@@ -198,10 +198,10 @@ typedef struct idkpt_stats {
 /* The layout above only ever GROWS at its end, and IDKPT_ABI_VERSION counts the growths (and every other change a host compiled against an older header could trip over: new
  * enum values of idkpt_buffer or idkpt_texture_format, new fields of idkpt_texture, new entry points: 5 = idkptComputeSky / idkptUpdateSky / idkptDownloadSky, 6 = idkptPresent / idkptDownloadDisplay / idkptGetDisplayDevicePtr,
  * 7 = idkptBloom / idkptGetBloomInfo / idkptDownloadBloom / idkptGetBloomDevicePtr, 8 = idkptUnprojectSky,
- * 9 = idkptSetPresentationSize / idkptGetPresentationSize / idkptGetBloomRoute / idkptGetBloomChainDevicePtr).  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
+ * 9 = idkptSetPresentationSize / idkptGetPresentationSize / idkptGetBloomRoute / idkptGetBloomChainDevicePtr, 10 = idkptDownloadTileClasses).  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
  * of ITS struct to idkptGetStatsSized and gets exactly that many bytes; idkptGetStats(ctx, out) is idkptGetStatsSized(ctx, out, sizeof(idkpt_stats)) of the header the LIBRARY
  * was built with — for hosts built from the same tree.  idkptGetAbiVersion() lets a host refuse a library older than the header it was written against. */
-#define IDKPT_ABI_VERSION 9
+#define IDKPT_ABI_VERSION 10
 
 /* ---- lifetime --------------------------------------------------------------------------- */
 /* new PathTracer(w,h,settings) (PathTracer.cs:170-212).  deviceCount = 1: the reference's situation, one GPU.
@@ -578,6 +578,16 @@ IDKPT_API int32_t idkptDownloadAliveQueue(idkpt_ctx* ctx, uint32_t* indices, siz
 /* enable=1: idkptRender keeps a copy of the primary-ray hit records (costs one 16 B/pixel device copy per sample) */
 IDKPT_API int32_t idkptEnablePrimaryHitCapture(idkpt_ctx* ctx, int32_t enable);
 IDKPT_API int32_t idkptDownloadPrimaryHits(idkpt_ctx* ctx, float* t, uint32_t* triangleId, float* baryXY, size_t pixelCount);
+/* Diagnostic / test hook (of the idkptCbrtProbe / idkptEnablePrimaryHitCapture kind; no reference equivalent, never needed for correct results): the classes the first-hit
+ * stage gave the 8x8 pixel tiles of the LAST LAUNCHED batch, as out[set][tileY * tilesX + tileX], one byte each (tiles of the context's local rows; launches what is still
+ * queued first; synchronises).  0 = the tile's pixels take the per-pixel path; 1..6 = every primary ray of the tile is a proven miss that sees face (class - 1) of a
+ * constant-per-face sky (+X, -X, +Y, -Y, +Z, -Z); 7 = a proven miss without a sky; 8 = a proven miss under a textured sky.  *sets is 1, or the batch size when the batch was
+ * classified per sample (a frame ring's cameras, scene versions); *sets is 0 — and nothing is written to out — when the batch ran without a classification (developer option
+ * "no_tile_cull", DoTraceLights, not the fast path, or nothing rendered since idkptSetSize).  out = NULL returns the three numbers only; otherwise bytes must equal
+ * sets * tilesX * tilesY.  One device only: of a multi-device context the tiles of member 0.
+ * The classification takes the apex of a tile's beam from ViewPos and the ray origins from InvView's translation: the two must agree to the few ulps a binary32 matrix
+ * inverse produces (idkptSetPerFrame / idkptSetPerFrameData); a host whose ViewPos is anything else than that translation is outside the contract. */
+IDKPT_API int32_t idkptDownloadTileClasses(idkpt_ctx* ctx, uint8_t* out, size_t bytes, int32_t* tilesX, int32_t* tilesY, int32_t* sets);
 
 /* ---- instrumentation -------------------------------------------------------------------- */
 IDKPT_API int32_t idkptGetStats(idkpt_ctx* ctx, idkpt_stats* outStats);

@@ -79,6 +79,10 @@ def lib():
         L.ref_r2_sequence.argtypes = [C.c_uint32, C.c_void_p]
         L.ref_ray_triangle.restype = C.c_int; L.ref_ray_triangle.argtypes = [C.c_void_p] * 7
         L.ref_ray_box.restype = C.c_int; L.ref_ray_box.argtypes = [C.c_void_p] * 5
+        # the first-hit stage taken apart (tests/adversarial_cameras.py): FirstHit's primary rays with the random draws as arguments; TraceRay's first box tests
+        L.ref_primary_rays.restype = None
+        L.ref_primary_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ref_first_box_tests.restype = None; L.ref_first_box_tests.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
         _LIB = L
     return _LIB
 

@@ -1032,4 +1032,65 @@ int ref_ray_triangle(const float* o, const float* d, const float* p0, const floa
 int ref_ray_box(const float* o, const float* d, const float* bmin, const float* bmax, float* t1)
 { v3 inv = V3(1.0f / d[0], 1.0f / d[1], 1.0f / d[2]); return RayBoxIntersect(V3(o[0], o[1], o[2]), inv, bmin, bmax, t1); }
 
+// ---- the first-hit stage taken apart (tests/adversarial_cameras.py) ----
+// The primary rays of FirstHit main (RenderSample above, FirstHit/compute.glsl:44-77) with the two random draws replaced by arguments: for every pixel (xy[2p], xy[2p + 1]) of
+// a W x H frame, every jitter (jit[2j], jit[2j + 1]) in place of (ox, oy) and every lens point (disk[2l], disk[2l + 1]) in place of SampleDisk's result, ray
+// (p * nJit + j) * nDisk + l: its origin, the direction the traversal is given — DecodeUnitVec of the stored EncodeUnitVec, as ShadeRay reads it — and the sky face SampleSky
+// selects for that direction (0-5: +X -X +Y -Y +Z -Z), taken from SampleSky itself on a sky whose face f has the colour f.
+void ref_primary_rays(const float* invProj, const float* invView, const float* viewPos3, float focalLength, float lenseRadius, int W, int H,
+                      size_t nPix, const int32_t* xy, size_t nJit, const float* jit, size_t nDisk, const float* disk, float* outOrigin, float* outDir, uint8_t* outFace)
+{
+    Scene faces; faces.skySize = 1; faces.sky.assign(24, 0.0f);
+    for (int f = 0; f < 6; f++) faces.sky[4 * (size_t)f] = (float)f;
+    #pragma omp parallel for schedule(static)
+    for (long long p = 0; p < (long long)nPix; p++) {
+        const int x = xy[2 * p], y = xy[2 * p + 1];
+        for (size_t j = 0; j < nJit; j++) {
+            const float ox = jit[2 * j], oy = jit[2 * j + 1];
+            v2 ndc = {((float)x + ox) / (float)W * 2.0f - 1.0f, ((float)y + oy) / (float)H * 2.0f - 1.0f};
+            const v3 camDir0 = GetWorldSpaceDirection(invProj, invView, ndc);
+            const v3 viewPos = V3(viewPos3[0], viewPos3[1], viewPos3[2]);
+            const v3 focalPoint = viewPos + camDir0 * focalLength;
+            for (size_t l = 0; l < nDisk; l++) {
+                const v3 pointOnLense = mat4_mul_xyz(invView, lenseRadius * disk[2 * l], lenseRadius * disk[2 * l + 1], 0.0f, 1.0f);
+                const v3 camDir = normalize(focalPoint - pointOnLense);
+                const v3 rd = DecodeUnitVec(EncodeUnitVec(camDir));
+                const size_t i = ((size_t)p * nJit + j) * nDisk + l;
+                outOrigin[3 * i] = pointOnLense.x; outOrigin[3 * i + 1] = pointOnLense.y; outOrigin[3 * i + 2] = pointOnLense.z;
+                outDir[3 * i] = rd.x; outDir[3 * i + 1] = rd.y; outDir[3 * i + 2] = rd.z;
+                if (outFace) outFace[i] = (uint8_t)SampleSky(faces, rd).x;
+            }
+        }
+    }
+}
+// Does a world ray pass one of the first box tests of TraceRay with T = FLOAT_MAX?  The instance loop: some instance's root test (IntersectBlas :32-39, the ray under that
+// instance's InvModel); useTlas: one of the two children of the TLAS root (:242-249), and always when the root is a leaf (entered unconditionally); never without a TLAS.
+void ref_first_box_tests(void* scene, int useTlas, size_t n, const float* origin, const float* dir, uint8_t* out)
+{
+    const Scene& s = *(Scene*)scene;
+    #pragma omp parallel for schedule(static)
+    for (long long i = 0; i < (long long)n; i++) {
+        Ray ray = {V3(origin[3 * i], origin[3 * i + 1], origin[3 * i + 2]), V3(dir[3 * i], dir[3 * i + 1], dir[3 * i + 2])};
+        bool pass = false; float t;
+        if (useTlas) {
+            if (!s.tlas.empty()) {
+                const GpuTlasNode& root = s.tlas[0];
+                if ((root.IsLeafAndChildOrInstanceId >> 31) == 1) pass = true;
+                else {
+                    const uint32_t id = root.IsLeafAndChildOrInstanceId & ((1u << 31) - 1);
+                    const v3 invDir = V3(1.0f / ray.d.x, 1.0f / ray.d.y, 1.0f / ray.d.z);
+                    for (uint32_t k = id; k < id + 2 && !pass; k++) pass = RayBoxIntersect(ray.o, invDir, s.tlas[k].Min, s.tlas[k].Max, &t) && t < REF_FLOAT_MAX;
+                }
+            }
+        } else for (size_t k = 0; k < s.instances.size() && !pass; k++) {
+            const GpuBlasInstance& inst = s.instances[k];
+            const Ray local = RayTransform(ray, s.xforms[inst.MeshTransformId].InvModel);
+            const v3 invDir = V3(1.0f / local.d.x, 1.0f / local.d.y, 1.0f / local.d.z);
+            const GpuBlasNode& root = s.nodes[(size_t)s.descs[inst.BlasId].NodeOffset + 1];
+            pass = RayBoxIntersect(local.o, invDir, root.Min, root.Max, &t) && t < REF_FLOAT_MAX;
+        }
+        out[i] = pass ? 1 : 0;
+    }
+}
+
 } // extern "C"
