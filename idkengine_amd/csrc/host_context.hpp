@@ -10,6 +10,30 @@ struct DevBuf {
     template <class T> T* as() const { return (T*)p; }
 };
 
+// Pinned, double-buffered staging of a small table every batch uploads (the per-sample scene versions, the per-sample cameras): no stream synchronisation per batch —
+// the host may run ahead of the GPU, and a half is filled again only once the copy that last read it has finished.  Allocated on first use.
+struct PinnedStage {
+    char* host = nullptr; hipEvent_t ev[2] = {nullptr, nullptr}; int half = 0;
+    // fill(half) writes `bytes` bytes, which are then copied to dst (kept at `capacity` bytes) in stream order
+    template <class Fill> hipError_t stage(DevBuf& dst, size_t capacity, size_t bytes, hipStream_t st, Fill&& fill)
+    {
+        hipError_t e;
+        if (!host) {
+            if ((e = hipHostMalloc((void**)&host, 2 * capacity, hipHostMallocDefault)) != hipSuccess) return e;
+            for (int i = 0; i < 2; i++) if ((e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming)) != hipSuccess) return e;
+            half = 0;
+        } else if ((e = hipEventSynchronize(ev[half])) != hipSuccess) return e;          // the copy that last read this half has finished
+        char* h = host + (size_t)half * capacity;
+        fill(h);
+        if ((e = dst.ensure(capacity)) != hipSuccess) return e;
+        if ((e = hipMemcpyAsync(dst.p, h, bytes, hipMemcpyHostToDevice, st)) != hipSuccess) return e;
+        if ((e = hipEventRecord(ev[half], st)) != hipSuccess) return e;
+        half ^= 1;
+        return hipSuccess;
+    }
+    void release() { if (host) (void)hipHostFree(host); for (hipEvent_t& e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; } host = nullptr; }
+};
+
 // idkptBloom (host_bloom.hpp): the buffers of one ring slot — RGBA16F levels of the down and the up chain, the expanded RGBA32F image — and what the last bloom made of them
 struct BloomSlot {
     DevBuf down, up, out; size_t downBytes = 0, upBytes = 0, outBytes = 0;   // (bytes in front of each buffer's guard)
@@ -154,7 +178,7 @@ struct dev_ctx {
     int verSlots = 1; size_t vbytes[VB_COUNT] = {0}, vstride[VB_COUNT] = {0}; int valloc[VB_COUNT] = {1, 1, 1, 1, 1}, vcur[VB_COUNT] = {0};
     uint64_t lastMask[VB_COUNT] = {0};               // slots the last launched batch reads (a deferred last bounce still does: finish_deferred)
     uint8_t lastSlots[VB_COUNT] = {0}; bool lastMulti = false;   // ... the one set of slots of a single-version batch, or "per sample: verTab"
-    DevBuf verTab; uint32_t* hVerTab = nullptr; hipEvent_t evVer[2] = {nullptr, nullptr}; int verHalf = 0;   // per-sample version table of the batch being launched (pinned, double-buffered staging)
+    DevBuf verTab; PinnedStage verStage;               // per-sample version table of the batch being launched, and its staging
     char* hStage = nullptr; hipEvent_t evStage[4] = {nullptr, nullptr, nullptr, nullptr}; int stageNext = 0;   // pinned ring for small host -> device updates (joint matrices, transforms): no stream synchronisation per call
     char* hSkyStage = nullptr; size_t hSkyStageBytes = 0; hipEvent_t evSkyStage = nullptr;   // pinned staging of the host faces idkptUpdateSky uploads (its copy is asynchronous: the call does not wait for the stream); the event = the last copy that read it
     hipEvent_t evSky = nullptr;                       // multi-device contexts: this member's last write to / last peer read of its sky (idkpt_api.hpp idkptUpdateSky)
@@ -187,7 +211,8 @@ struct dev_ctx {
     double traceMsAcc = 0.0; uint64_t traceLaunchesAcc = 0;
     int lastQueueSide = 0; int lastQueueCountSlot = 0; bool lastFast = false, lastNeedsRegen = false, lastTileClass = false /* tileClass holds the classification of the last launched batch (k_regen_culled) */; int lastBatch = 1; Frame lastFrame;
     int maxBatch = 1; uint32_t Npad = 0; std::vector<PendingSample> pending; DevBuf bases, qwork; uint32_t* hBases = nullptr; uint32_t* dBasesMirror = nullptr;
-    float* hCams = nullptr; hipEvent_t evCams[2] = {nullptr, nullptr}; int camHalf = 0;   // pinned, double-buffered staging of the per-sample cameras (frame ring)    // member of a multi-device context (idkpt_api.hpp): samples are only queued (the group launches all members together), per-bounce events tell
+    PinnedStage camStage;                                // staging of camTab: the per-sample cameras (frame ring)
+    // member of a multi-device context (idkpt_api.hpp): samples are only queued (the group launches all members together), per-bounce events tell
     // the members that own later rows when this member's alive counts of a bounce are final, and the group supplies the slot bases
     bool grouped = false, inGroupFlush = false; int groupIndex = 0;
     hipEvent_t* evBounce = nullptr;                              // [MAX_DEPTH_SLOTS]; evBounce[j] = bases[j] (alive counts entering bounce j) written

@@ -257,12 +257,10 @@ static int32_t dev_Present(dev_ctx* ctx, int32_t slot, int32_t image, const idkp
     if (scaled) { p.W = ctx->presW; p.rows = ctx->presH; }      // (the whole frame on this device: present_validate)
     const uint32_t threads = (uint32_t)(((size_t)p.W + 3) / 4 * p.rows);
     if (threads && scaled) {
-        if (format == IDKPT_DISPLAY_RGBA32F) hipLaunchKernelGGL((k_present_scaled<true>), dim3((threads + 255u) / 256u), dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, image, slot), ctx->W, ctx->H, (const float4*)dAdd0, (const float4*)dAdd1, buf.p, p);
-        else hipLaunchKernelGGL((k_present_scaled<false>), dim3((threads + 255u) / 256u), dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, image, slot), ctx->W, ctx->H, (const float4*)dAdd0, (const float4*)dAdd1, buf.p, p);
+        with_flag(format == IDKPT_DISPLAY_RGBA32F, [&](auto F32) { launch(k_present_scaled<F32>, dim3((threads + 255u) / 256u), dim3(256), 0, ctx->stream, image_ptr(ctx, image, slot), ctx->W, ctx->H, (const float4*)dAdd0, (const float4*)dAdd1, buf.p, p); });
         HIPC(hipGetLastError());
     } else if (threads) {
-        if (format == IDKPT_DISPLAY_RGBA32F) hipLaunchKernelGGL((k_present<true>), dim3((threads + 255u) / 256u), dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, image, slot), (const float4*)dAdd0, (const float4*)dAdd1, buf.p, p);
-        else hipLaunchKernelGGL((k_present<false>), dim3((threads + 255u) / 256u), dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, image, slot), (const float4*)dAdd0, (const float4*)dAdd1, buf.p, p);
+        with_flag(format == IDKPT_DISPLAY_RGBA32F, [&](auto F32) { launch(k_present<F32>, dim3((threads + 255u) / 256u), dim3(256), 0, ctx->stream, image_ptr(ctx, image, slot), (const float4*)dAdd0, (const float4*)dAdd1, buf.p, p); });
         HIPC(hipGetLastError());
     }
     ctx->dispFmt[slot] = format;

@@ -138,10 +138,7 @@ static int32_t dev_Destroy(dev_ctx* ctx)
     if (ctx->hUni) (void)hipHostFree(ctx->hUni);
     if (ctx->hPkStats) (void)hipHostFree(ctx->hPkStats);
     if (ctx->hBases) (void)hipHostFree(ctx->hBases);
-    if (ctx->hCams) (void)hipHostFree(ctx->hCams);
-    for (int i = 0; i < 2; i++) if (ctx->evCams[i]) (void)hipEventDestroy(ctx->evCams[i]);
-    if (ctx->hVerTab) (void)hipHostFree(ctx->hVerTab);
-    for (int i = 0; i < 2; i++) if (ctx->evVer[i]) (void)hipEventDestroy(ctx->evVer[i]);
+    ctx->camStage.release(); ctx->verStage.release();
     if (ctx->hStage) (void)hipHostFree(ctx->hStage);
     if (ctx->hSkyStage) (void)hipHostFree(ctx->hSkyStage);
     if (ctx->evSkyStage) (void)hipEventDestroy(ctx->evSkyStage);

@@ -40,6 +40,7 @@ using namespace ptd;
 #include "bvh_gpu_full.hpp"
 
 // =================================================================================================== host side (one file per concern, in dependency order)
+#include "host_kernel.hpp"
 #include "host_context.hpp"
 #include "walk_plan.hpp"
 #include "host_launch.hpp"
