@@ -491,7 +491,25 @@ IDKPT_API int32_t idkptGetDisplayDevicePtr(idkpt_ctx* ctx, int32_t slot, void** 
  * explicit level, uv = (texel + 0.5) / size of the written level, f = u * size - 0.5 + offset, floor, fractional weights, clamped indices, mix(x, y, a) = x (1 - a) + y a.
  * Storage (the contract): levels are R16G16B16A16Float like the reference's, 8 bytes per texel in memory order R, G, B, A with alpha 1.0 (0x3C00).  float -> half ROUNDS
  * TOWARD ZERO; a finite value beyond 65504 is stored as 65504; subnormal halves are produced; +-Inf stays, NaN becomes a quiet NaN.  (Mesa llvmpipe stores every
- * texel of the test fixture by this rule.)
+ * texel of the test fixtures by this rule, the adversarial ones included: observed there are -Inf kept as -Inf and NaN stored as sign | 0x7E00 with llvmpipe's own
+ * sign; a +Inf never reaches a store of the reference's chain, Prefilter's min(MaxColor, c) removes it in the first pass.  tests/test_adversarial_pixels_glref.py.)
+ * On the same non-finite texels the reference's tonemap shader on llvmpipe also stores finite texels only, but other colours than this library on most texels a NaN or
+ * an infinity reaches (GLSL leaves them undefined), and its texture() lets a texel of FLT_MAX or Inf leak into the neighbouring texel centres (profiles/display_nonfinite.md).
+ * Non-finite and extreme texels (the path tracer can leave +Inf and NaN in an image: an emission that overflows, inf * 0 on a black throughput).  No texel VALUE feeds an
+ * address in idkptPresent or idkptBloom, so such a texel changes values only, and only where a filter tap fetches it.  GLSL leaves min / max / clamp of a NaN undefined, so
+ * the reference's shader cannot settle what follows; this library fixes it (tests/adversarial_pixels.py, profiles/display_nonfinite.md):
+ *   idkptPresent, both sizes   EVERY stored texel is finite, in both formats, for every input bit pattern.  The shader's max(.., 0) and clamp are fmaxf / fminf, which drop
+ *                  a NaN operand: a NaN, -Inf or negative channel acts as 0 at the head of AgX_DS (and in the clamp of DoTonemapAndSrgbTransform = 0); +Inf saturates
+ *                  (DualSection(+Inf) = Peak); the NaN of inf - inf inside sRGB_to_adjusted * v becomes 0 in the clamp behind DualSection.  The sum ((0 + s0) + s1) + s2
+ *                  is plain binary32: it may overflow to +-Inf, and +Inf + -Inf is a NaN, handled as above.  No NaN is ever converted to a byte.
+ *   idkptBloom     min and max by their GLSL definitions, min(x, y) = y < x ? y : x, max(x, y) = x < y ? y : x: Prefilter's min(MaxColor, c) turns a NaN channel into
+ *                  MaxColor and +Inf into MaxColor; a -Inf channel under s = 0 becomes -inf * 0 = NaN.  Levels can therefore hold +-Inf and NaN halves.
+ *   the half store the rule above for every bit pattern: +-Inf stays +-Inf; a NaN of any payload becomes sign | 0x7E00 — the sign is the binary32 NaN's, and the sign of a
+ *                  NaN that arithmetic produced is the platform's (inf * 0: positive on the device, negative on x86), so only the low 15 bits are portable.
+ *   the filter     mix(x, y, a) = x * (1 - a) + y * a as written, everywhere (bloom's taps, the expanded image, Sampler0 of the scaled idkptPresent): an Inf texel under a
+ *                  weight of exactly 0 gives Inf * 0 = NaN — which the scaled idkptPresent then shows as 0, not as a saturated texel — and clamped indices that fetch one
+ *                  Inf texel twice give Inf.  A non-finite texel reaches exactly the texels whose taps fetch it. */
+/* (continued: the expanded image and the scope of idkptBloom)
  * The expanded image: what the tonemap shader reads, texture(Sampler1, (pixel + 0.5) / size) — up level 0 magnified bilinearly (linear, clamp to edge) — for every pixel
  * of the frame as RGBA32F (rgb, 1.0).  idkptGetBloomDevicePtr returns it; passed as idkptPresent's dAdd0 it gives the engine's default displayed frame with nothing
  * computed on the host.

@@ -8,7 +8,10 @@ Every function takes dtype:
 Conventions (GLSL leaves the filter's arithmetic to the implementation; hence a measured bound, tests/test_bloom_ref.py): textureLod / textureLodOffset = linear
 filter, clamp to edge, explicit level; uv = (texel + 0.5) / size of the written level; f = u * size - 0.5 + offset, i0 = floor(f), weight f - i0, texels i0 and
 i0 + 1 with clamped indices; mix(x, y, a) = x * (1 - a) + y * a, x first, then y.
-Storage: levels are RGBA16F bits, (h, w, 4) uint16, alpha 0x3C00.  rtz_half is the header's rule: round toward zero, finite overflow -> 65504, subnormals produced.
+Storage: levels are RGBA16F bits, (h, w, 4) uint16, alpha 0x3C00.  rtz_half is the header's rule: round toward zero, finite overflow -> 65504, subnormals produced,
++-Inf kept, NaN -> sign | 0x7E00.
+Non-finite texels (include/idkpt.h "Non-finite and extreme texels"; tests/adversarial_pixels.py): min / max are GLSL's definitions, y < x ? y : x and x < y ? y : x
+(_min / _max: Prefilter turns a NaN channel into MaxColor), and the filter's mix is evaluated as written, Inf * 0 = NaN under a weight of exactly 0.
 
 down_pass / up_pass / expand run ONE pass from given input bits; chain runs everything from an image.  CASES are the fixture's; input_image(case) its inputs."""
 import os
@@ -74,13 +77,16 @@ def input_image(case):
 
 # ---- storage
 def rtz_half(v):
-    """float array (binary32 or binary64) -> binary16 bits, rounded toward zero; a finite value beyond 65504 -> 65504 (0x7BFF); subnormal halves are produced."""
+    """float array (binary32 or binary64) -> binary16 bits, rounded toward zero; a finite value beyond 65504 -> 65504 (0x7BFF); subnormal halves are produced;
+    +-Inf stays; a NaN becomes sign | 0x7E00 whatever its payload (f32_to_f16_rtz)."""
     v = np.asarray(v)
-    with np.errstate(over="ignore"):
+    with np.errstate(over="ignore", invalid="ignore"):
         h = v.astype(np.float16)                                   # round to nearest even, overflow to Inf
+        away = (np.abs(h.astype(np.float64)) > np.abs(v.astype(np.float64))) & np.isfinite(v)
     bits = h.view(np.uint16).copy()
-    away = (np.abs(h.astype(np.float64)) > np.abs(v.astype(np.float64))) & np.isfinite(v)
     bits[away] -= 1                                                # one step toward zero (sign-magnitude; Inf - 1 = 65504)
+    nan = np.isnan(v)
+    bits[nan] = np.where(np.signbit(v[nan]), 0xFE00, 0x7E00).astype(np.uint16)
     return bits
 
 
@@ -138,15 +144,25 @@ def _upsample(src, dw, dh, dt):
     return r / dt(16.0)
 
 
+def _min(x, y):
+    """GLSL's min by its definition, y < x ? y : x (bloomt::minf): a NaN x is returned, a NaN y is dropped"""
+    return np.where(y < x, y, x)
+
+
+def _max(x, y):
+    """GLSL's max by its definition, x < y ? y : x (bloomt::maxf)"""
+    return np.where(x < y, y, x)
+
+
 def _prefilter(c, max_color, threshold, dt):
     knee = dt(np.float32(KNEE)) if dt is np.float32 else dt(KNEE)
     max_color, threshold = dt(np.float32(max_color)), dt(np.float32(threshold))      # the settings are binary32 values
-    c = np.where(c < max_color, c, max_color)                                        # min(vec3(maxColor), color)
-    b = np.maximum(np.maximum(c[..., 0], c[..., 1]), c[..., 2])
+    c = _min(max_color, c)                                                           # min(vec3(maxColor), color)
+    b = _max(_max(c[..., 0], c[..., 1]), c[..., 2])
     cx, cy, cz = threshold - knee, knee * dt(2.0), dt(0.25) / knee
-    rq = np.minimum(np.maximum(b - cx, dt(0.0)), cy)
+    rq = _min(_max(b - cx, dt(0.0)), cy)
     rq = (rq * rq) * cz
-    s = np.maximum(rq, b - threshold) / np.maximum(b, dt(0.0001))
+    s = _max(rq, b - threshold) / _max(b, dt(0.0001))
     return c * s[..., None]
 
 

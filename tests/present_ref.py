@@ -9,6 +9,9 @@ Conventions both restatements share (GLSL leaves them to the implementation; hen
   mat3 is column-major, m[c][r]; M * v sums M[0][r] v.x + M[1][r] v.y + M[2][r] v.z left to right, A * B likewise over k; inverse(mat3) is cofactors divided by the determinant;
   mix(x, y, a) = x * (1 - a) + y * a; dot sums left to right; pow(2, e), exp and pow(x, 1 / 2.4) are the library functions of the dtype.
 quantise(x) is the header's rule for IDKPT_DISPLAY_RGBA8: (uint8) rint(min(max(x, 0), 1) * 255.0f) in binary32, alpha 255.
+Non-finite texels (include/idkpt.h "Non-finite and extreme texels"; tests/adversarial_pixels.py): every max(.., 0) and clamp is fmaxf / fminf (np.fmax / np.fmin), which drop
+a NaN operand, as the kernel's gmax / gmin / gclamp do: a NaN or negative input acts as 0, the NaN of inf - inf inside M * v becomes 0 in the clamp behind DualSection, and every
+stored texel is finite; quantise never converts a NaN to an integer.
 input_image() / bloom_image() are the fixture's inputs (70 x 40, by formula), CASES its settings."""
 import os
 import numpy as np
@@ -146,23 +149,23 @@ def present(img, settings, add0=None, add1=None, dtype=np.float32, first_row=0):
     hdr = hdr + (add1[..., :3].astype(f) if add1 is not None else f(0.0))
     if int(settings[5]):
         m, minv, e2 = matrices(settings, f)
-        c = np.maximum(hdr, f(0.0)) * e2
+        c = np.fmax(hdr, f(0.0)) * e2                                        # gmax: a NaN operand is dropped (fmaxf)
         c = np.stack(_mul_mv(m, [c[..., 0], c[..., 1], c[..., 2]]), -1)
         S = peak * lin
         with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
             C = peak / (peak - S)
             upper = peak - (peak - S) * np.exp((-C * (c - S)) / peak)
         c = np.where(c < S, c, upper)
-        c = np.minimum(np.maximum(c, f(0.0)), f(1.0))
+        c = np.fmin(np.fmax(c, f(0.0)), f(1.0))
         des = c[..., 0] * f(0.2126729) + c[..., 1] * f(0.7151522) + c[..., 2] * f(0.0721750)
         c = des[..., None] * (f(1.0) - sat) + c * sat
-        c = np.minimum(np.maximum(c, f(0.0)), f(1.0))
+        c = np.fmin(np.fmax(c, f(0.0)), f(1.0))
         c = np.stack(_mul_mv(minv, [c[..., 0], c[..., 1], c[..., 2]]), -1)
         with np.errstate(invalid="ignore"):
             higher = f(1.055) * np.power(c, f(1.0) / f(2.4)) - f(0.055)
         c = np.where(c < f(0.0031308), c * f(12.92), higher)
     else:
-        c = np.minimum(np.maximum(hdr, f(0.0)), f(1.0))
+        c = np.fmin(np.fmax(hdr, f(0.0)), f(1.0))
     d = dither_values(f)
     xs = np.arange(w) % 8; ys = (np.arange(h) + first_row) % 8
     c = c + d[xs[None, :], ys[:, None]][..., None]
@@ -175,7 +178,7 @@ def quantise(x):
     """IDKPT_DISPLAY_RGBA8 of the RGBA32F display `x` ((.., 4) float32): the header's rule, in binary32; alpha 255."""
     x = np.asarray(x)
     assert x.dtype == np.float32
-    q = np.rint(np.minimum(np.maximum(x, np.float32(0.0)), np.float32(1.0)) * np.float32(255.0)).astype(np.uint8)
+    q = np.rint(np.fmin(np.fmax(x, np.float32(0.0)), np.float32(1.0)) * np.float32(255.0)).astype(np.uint8)   # fmaxf / fminf: no NaN reaches the integer conversion
     q[..., 3] = 255
     return q
 

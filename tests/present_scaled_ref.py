@@ -80,7 +80,7 @@ def no_tonemap_display(hdr):
     ph, pw = hdr.shape[:2]
     d = P.dither_values(np.float32)
     out = np.ones((ph, pw, 4), np.float32)
-    out[..., :3] = np.minimum(np.maximum(hdr, np.float32(0.0)), np.float32(1.0)) + d[(np.arange(pw) % 8)[None, :], (np.arange(ph) % 8)[:, None]][..., None]
+    out[..., :3] = np.fmin(np.fmax(hdr, np.float32(0.0)), np.float32(1.0)) + d[(np.arange(pw) % 8)[None, :], (np.arange(ph) % 8)[:, None]][..., None]
     return out
 
 
