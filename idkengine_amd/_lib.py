@@ -19,6 +19,7 @@ SYMBOLS = [
     "idkptPresent", "idkptDownloadDisplay", "idkptGetDisplayDevicePtr",
     "idkptBloom", "idkptGetBloomInfo", "idkptDownloadBloom", "idkptGetBloomDevicePtr",
     "idkptSetPresentationSize", "idkptGetPresentationSize", "idkptGetBloomRoute", "idkptGetBloomChainDevicePtr",
+    "idkptCollideSpheres", "idkptCollideSpheresDevice",
 ]
 
 _lib = None
@@ -48,6 +49,7 @@ def load():
         "idkptPresent": [vp, i32, i32, vp, i32, vp, vp], "idkptDownloadDisplay": [vp, i32, vp, sz], "idkptGetDisplayDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(sz)],
         "idkptBloom": [vp, i32, i32, vp], "idkptGetBloomInfo": [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)], "idkptDownloadBloom": [vp, i32, i32, i32, vp, sz], "idkptGetBloomDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(sz)],
         "idkptSetPresentationSize": [vp, i32, i32], "idkptGetPresentationSize": [vp, C.POINTER(i32), C.POINTER(i32)], "idkptGetBloomRoute": [vp, i32, C.POINTER(i32)], "idkptGetBloomChainDevicePtr": [vp, i32, i32, C.POINTER(vp), C.POINTER(sz)],
+        "idkptCollideSpheres": [vp, vp, vp, sz, vp], "idkptCollideSpheresDevice": [vp, vp, vp, sz, vp],
         "idkptRefitBlas": [vp, i32], "idkptUploadUnskinnedVertices": [vp, vp, i32], "idkptSkin": [vp, u32, u32, u32, u32],
         "idkptDownloadBuffer": [vp, i32, sz, sz, vp], "idkptResetAccumulation": [vp], "idkptSetSampleSequence": [vp, u32, u32], "idkptGetAccumulatedSamples": [vp, C.POINTER(u32)],
         "idkptRender": [vp], "idkptSynchronize": [vp], "idkptDownload": [vp, i32, vp, sz], "idkptDownloadRays": [vp, vp, sz],

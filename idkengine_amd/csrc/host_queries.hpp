@@ -1,4 +1,4 @@
-// host_queries.hpp — idkptTraceRays / idkptTraceShadows (kernels_query.hpp) on the traversal kernels' scheduler.
+// host_queries.hpp — idkptTraceRays / idkptTraceShadows (kernels_query.hpp) on the traversal kernels' scheduler, and idkptCollideSpheres (kernels_collide.hpp).
 // Part of the single translation unit idkpt.hip (included there, in this order).
 #pragma once
 
@@ -107,3 +107,45 @@ static int32_t dev_TraceShadows(dev_ctx* ctx, const idkpt_shadow_params* p, cons
     return IDKPT_OK;
 }
 static int32_t dev_TraceShadowsDevice(dev_ctx* ctx, const idkpt_shadow_params* p, const float* dDepth, const float* dNormalOct, float* dVisibility) { return dev_TraceShadows(ctx, p, dDepth, dNormalOct, dVisibility, true); }
+
+// idkptCollideSpheres / idkptCollideSpheresDevice (kernels_collide.hpp).  Issue only, like dev_TraceRaysIssue: the caller synchronises; `out` must stay valid until then.
+static int32_t dev_CollideSpheresIssue(dev_ctx* ctx, const idkpt_collide_settings* set, const idkpt_moving_sphere* spheres, size_t count, idkpt_sphere_collision* out, bool devicePtrs = false)
+{
+    if (!ctx) return IDKPT_ERR_INVALID_ARGUMENT;
+    if (!ctx->haveScene) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptCollideSpheres: no scene uploaded");
+    REQUIRE(set != nullptr, "idkptCollideSpheres: null settings");
+    REQUIRE(count == 0 || (spheres && out), "idkptCollideSpheres: null spheres/out");
+    REQUIRE(count < (1ull << 31), "idkptCollideSpheres: too many spheres in one call");
+    REQUIRE(set->Response >= IDKPT_COLLIDE_NONE && set->Response <= IDKPT_COLLIDE_REFLECT, "idkptCollideSpheres: unknown Response");
+    REQUIRE(set->TestSteps >= 1 && set->TestSteps <= 64, "idkptCollideSpheres: TestSteps must be 1..64");
+    REQUIRE(set->RecursiveSteps >= 0 && set->RecursiveSteps <= 64, "idkptCollideSpheres: RecursiveSteps must be 0..64");
+    REQUIRE(std::isfinite(set->EpsilonNormalOffset), "idkptCollideSpheres: EpsilonNormalOffset must be finite");
+    REQUIRE(!devicePtrs || (((uintptr_t)spheres | (uintptr_t)out) & 15u) == 0, "idkptCollideSpheresDevice: device pointers must be 16-byte aligned");
+    if (set->UseTlas && ctx->tlasCount == 0) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptCollideSpheres: UseTlas set but no TLAS nodes uploaded");
+    if (count == 0) return IDKPT_OK;
+    HIPC(hipSetDevice(ctx->device));
+    FLUSH_KEEP();
+    Frame f; size_t ldsBytes; uint32_t grid; int rc = query_frame(ctx, f, ldsBytes, grid); if (rc) return rc;
+    f.useTlas = set->UseTlas ? 1 : 0;                                       // (this query's own choice, not the render setting: the LDS rows follow it)
+    { int wavesPerCU = 1; rc = trace_lds(ctx, f, f.useTlas ? f.tlasCap : 0, 0, ldsBytes, wavesPerCU); if (rc) return rc; }
+    DScene s = make_dscene(ctx);
+    hipStream_t st = ctx->stream;
+    const idkpt_moving_sphere* dIn = spheres; idkpt_sphere_collision* dOut = out;
+    if (!devicePtrs) {
+        HIPC(ctx->queryIn.ensure(count * sizeof(idkpt_moving_sphere))); HIPC(ctx->queryOut.ensure(count * sizeof(idkpt_sphere_collision)));
+        HIPC(hipMemcpyAsync(ctx->queryIn.p, spheres, count * sizeof(idkpt_moving_sphere), hipMemcpyHostToDevice, st));
+        dIn = ctx->queryIn.as<idkpt_moving_sphere>(); dOut = ctx->queryOut.as<idkpt_sphere_collision>();
+    }
+    launch(k_collide_spheres, dim3((uint32_t)((count + WAVE - 1) / WAVE)), dim3(WAVE), ldsBytes, st, s, f, *set, dIn, dOut, (uint32_t)count);
+    HIPC(hipGetLastError());
+    if (!devicePtrs) HIPC(hipMemcpyAsync(out, ctx->queryOut.p, count * sizeof(idkpt_sphere_collision), hipMemcpyDeviceToHost, st));
+    return IDKPT_OK;
+}
+static int32_t dev_CollideSpheresDevice(dev_ctx* ctx, const idkpt_collide_settings* set, const idkpt_moving_sphere* dSpheres, size_t count, idkpt_sphere_collision* dOut) { return dev_CollideSpheresIssue(ctx, set, dSpheres, count, dOut, true); }
+static int32_t dev_CollideSpheres(dev_ctx* ctx, const idkpt_collide_settings* set, const idkpt_moving_sphere* spheres, size_t count, idkpt_sphere_collision* out)
+{
+    int rc = dev_CollideSpheresIssue(ctx, set, spheres, count, out); if (rc) return rc;
+    if (count == 0) return IDKPT_OK;
+    SYNC_CHECKED();
+    return IDKPT_OK;
+}

@@ -26,6 +26,7 @@ using namespace ptd;
 #include "kernels_packet.hpp"
 #include "kernels_trace_split.hpp"
 #include "kernels_query.hpp"
+#include "kernels_collide.hpp"
 #include "kernels_shade.hpp"
 #include "kernels_trace_fused.hpp"
 #include "kernels_queue.hpp"

@@ -785,6 +785,30 @@ int32_t idkptTraceShadowsDevice(idkpt_ctx* c, const idkpt_shadow_params* p, cons
     return gfail(c, IDKPT_ERR_INVALID_OPERATION, "idkptTraceShadowsDevice: device pointers belong to one device; use a single-device context (or idkptTraceShadows)");
 }
 
+// sphere collision queries are independent like ray queries: one contiguous piece per device
+int32_t idkptCollideSpheres(idkpt_ctx* c, const idkpt_collide_settings* set, const idkpt_moving_sphere* spheres, size_t count, idkpt_sphere_collision* out)
+{
+    if (!c) return IDKPT_ERR_INVALID_ARGUMENT;
+    ONE(dev_CollideSpheres(m, set, spheres, count, out));
+    GREQ(set != nullptr, "idkptCollideSpheres: null settings");
+    GREQ(count == 0 || (spheres && out), "idkptCollideSpheres: null spheres/out");
+    if (count == 0) { int rc = dev_CollideSpheresIssue(c->dev[0], set, spheres, 0, out); return rc ? mfail(c, c->dev[0], rc) : IDKPT_OK; }   // (the refusals of an empty batch)
+    GFLUSH();
+    const size_t n = c->n(), per = (count + n - 1) / n;
+    for (size_t d = 0; d < n; d++) {
+        const size_t first = std::min(count, d * per), cnt = std::min(count, first + per) - first;
+        if (cnt == 0) continue;
+        int rc = dev_CollideSpheresIssue(c->dev[d], set, spheres + first, cnt, out + first); if (rc) { (void)group_sync(c); return mfail(c, c->dev[d], rc); }
+    }
+    return group_sync(c);
+}
+int32_t idkptCollideSpheresDevice(idkpt_ctx* c, const idkpt_collide_settings* set, const idkpt_moving_sphere* dSpheres, size_t count, idkpt_sphere_collision* dOut)
+{
+    if (!c) return IDKPT_ERR_INVALID_ARGUMENT;
+    ONE(dev_CollideSpheresDevice(m, set, dSpheres, count, dOut));
+    return gfail(c, IDKPT_ERR_INVALID_OPERATION, "idkptCollideSpheresDevice: device pointers belong to one device; use a single-device context (or idkptCollideSpheres)");
+}
+
 int32_t idkptSetFrameRing(idkpt_ctx* c, int32_t frames) { REPLICATE(SetFrameRing, frames); }
 int32_t idkptBeginFrame(idkpt_ctx* c, int32_t* outSlot)
 {

@@ -278,6 +278,21 @@ assert RayQuery.itemsize == 32 and RayHit.itemsize == 32
 IDKPT_TRACE_ANY_HIT, IDKPT_TRACE_LIGHTS = 1, 2
 
 
+# sphere collision queries (include/idkpt.h: idkpt_collide_settings, idkpt_moving_sphere, idkpt_sphere_collision, enum idkpt_collide_response)
+IDKPT_COLLIDE_NONE, IDKPT_COLLIDE_SLIDE, IDKPT_COLLIDE_REFLECT = 0, 1, 2
+MovingSphere = np.dtype([("PrevPosition", "<f4", 3), ("Radius", "<f4"), ("Position", "<f4", 3), ("_pad0", "<u4"), ("Velocity", "<f4", 3), ("_pad1", "<u4")])
+SphereCollision = np.dtype([("Position", "<f4", 3), ("HitCount", "<u4"), ("Velocity", "<f4", 3), ("TriangleId", "<u4"), ("Center", "<f4", 3), ("BlasInstanceId", "<u4"),
+                            ("SlidingNormal", "<f4", 3), ("PenetrationDepth", "<f4"), ("TriNormal", "<f4", 3), ("Distance", "<f4"), ("TriCollidingPoint", "<f4", 3), ("_pad", "<u4")])
+assert MovingSphere.itemsize == 48 and SphereCollision.itemsize == 96
+
+
+class CollideSettings(C.Structure):
+    _fields_ = [("TestSteps", C.c_int32), ("RecursiveSteps", C.c_int32), ("EpsilonNormalOffset", C.c_float), ("Response", C.c_int32), ("UseTlas", C.c_int32), ("_pad", C.c_int32 * 3)]
+
+
+assert C.sizeof(CollideSettings) == 32
+
+
 class ShadowParams(C.Structure):
     _fields_ = [("InvProjView", C.c_float * 16), ("TaaJitter", C.c_float * 2), ("Width", C.c_int32), ("Height", C.c_int32),
                 ("LightIndex", C.c_int32), ("RayTracingSamples", C.c_int32), ("NoiseIndex", C.c_uint32), ("_pad0", C.c_uint32)]

@@ -31,7 +31,7 @@ class PathTracer:
             raise IdkPtError("no HIP device visible: the path tracer has no CPU fallback")
         ctx = C.c_void_p()
         ids = list(devices) if devices else [device]
-        self.device_count = len(ids)
+        self.device_count = len(ids); self.device_ids = ids
         if self.device_count > 1 and (row_modulo, row_remainder) != (1, 0):
             raise IdkPtError("a multi-device context deals its rows itself")
         dev = (C.c_int32 * len(ids))(*ids)
@@ -254,6 +254,33 @@ class PathTracer:
         """idkptTraceShadowsDevice: the three images are device pointers (W*H floats, W*H*2 floats, W*H floats in/out).  Asynchronous in stream order."""
         import ctypes as C
         self._check(self._L.idkptTraceShadowsDevice(self._ctx, C.addressof(params), int(d_depth), int(d_normal_oct), int(d_visibility)))
+
+    def CollideSpheres(self, spheres, test_steps=1, recursive_steps=8, epsilon=0.001, response=0, use_tlas=False):
+        """idkptCollideSpheres: Intersections.SceneVsMovingSphereCollisionRoutine (Source/Shapes/Intersections.cs:491-593) for every sphere, on the resident BVH.
+        spheres: array of gputypes.MovingSphere; returns an array of gputypes.SphereCollision.  response: 0 none, 1 slide (the camera), 2 reflect (the lights).
+        A contiguous torch tensor on this context's device (count x 48 bytes, any dtype) goes through idkptCollideSpheresDevice instead: no PCIe round trip, the
+        results come back as a device tensor of count x 24 float32 words (gputypes.SphereCollision records)."""
+        import ctypes as C
+        from . import gputypes as T
+        st = T.CollideSettings(int(test_steps), int(recursive_steps), float(epsilon), int(response), 1 if use_tlas else 0)
+        if hasattr(spheres, "data_ptr"):
+            import torch
+            if not spheres.is_cuda or spheres.device.index != self.device_ids[0]:
+                raise ValueError(f"CollideSpheres: the tensor lives on {spheres.device}, this context on device {self.device_ids[0]}")
+            if not spheres.is_contiguous():
+                raise ValueError("CollideSpheres: the tensor must be contiguous")
+            nbytes = spheres.numel() * spheres.element_size()
+            if nbytes % T.MovingSphere.itemsize:
+                raise ValueError("CollideSpheres: the tensor is not a whole number of 48-byte gputypes.MovingSphere records")
+            count = nbytes // T.MovingSphere.itemsize
+            out = torch.empty((count, T.SphereCollision.itemsize // 4), dtype=torch.float32, device=spheres.device)
+            self._check(self._L.idkptCollideSpheresDevice(self._ctx, C.addressof(st), spheres.data_ptr() if count else 0, count, out.data_ptr() if count else 0))
+            self.synchronize()
+            return out
+        s = np.ascontiguousarray(spheres, T.MovingSphere).reshape(-1)
+        out = np.zeros(len(s), T.SphereCollision)
+        self._check(self._L.idkptCollideSpheres(self._ctx, C.addressof(st), s.ctypes.data, len(s), out.ctypes.data))
+        return out
 
     def RefitBlas(self, blas_id):
         self._check(self._L.idkptRefitBlas(self._ctx, blas_id))

@@ -131,6 +131,43 @@ typedef struct idkpt_shadow_params {
     uint32_t _pad0;
 } idkpt_shadow_params;
 
+/* ---- sphere collision queries: Intersections.SceneVsMovingSphereCollisionRoutine (Source/Shapes/Intersections.cs:491-593) on the resident BVH ---- */
+/* SceneVsMovingSphereSettings (Intersections.cs:12-17) + what the reference's two callers add around the routine.  Response: what the caller's callback does to the
+ * destination and the velocity after a hit — 0 nothing (the destination stays fixed), 1 slide (Camera.CollisionDetection, Camera.cs:158-167: Plane.Project),
+ * 2 reflect (LightManager.CollisionDetection, Render/LightManager.cs:247-256: Plane.Reflect).  UseTlas is BVH.CpuUseTlas (Bvh/BVH.cs:157): TLAS.Intersect instead of the
+ * instance loop; separate from idkpt_settings.UseTlas because the visiting order, and with it which triangle keeps a distance tie, differs. */
+enum idkpt_collide_response { IDKPT_COLLIDE_NONE = 0, IDKPT_COLLIDE_SLIDE = 1, IDKPT_COLLIDE_REFLECT = 2 };
+typedef struct idkpt_collide_settings {
+    int32_t TestSteps;            /* 1..64 (the GUI's slider stops at 20) */
+    int32_t RecursiveSteps;       /* 0..64 */
+    float   EpsilonNormalOffset;  /* finite */
+    int32_t Response;             /* enum idkpt_collide_response */
+    int32_t UseTlas;
+    int32_t _pad[3];
+} idkpt_collide_settings;
+IDKPT_STATIC_ASSERT(sizeof(idkpt_collide_settings) == 32, "idkpt_collide_settings");
+/* One sphere: `new Sphere(PrevPosition, Radius)` moving towards Position (the destination the routine takes by reference), with the Velocity the callback rewrites.
+ * Sphere values never feed an address.  Non-finite values follow the arithmetic: a NaN centre gives a NaN box, which overlaps nothing (every comparison is false);
+ * a +Inf radius gives corners at +-Inf, which overlap every world-space box, but Box.Transformed (Shapes/Box.cs:166-175) multiplies them with the zeros of a transform
+ * (Inf * 0 = NaN), so the box that enters a BLAS is a NaN box as well.  A finite radius that covers the scene visits every leaf. */
+typedef struct idkpt_moving_sphere {
+    float PrevPosition[3]; float Radius;
+    float Position[3];     uint32_t _pad0;
+    float Velocity[3];     uint32_t _pad1;
+} idkpt_moving_sphere;
+IDKPT_STATIC_ASSERT(sizeof(idkpt_moving_sphere) == 48, "idkpt_moving_sphere");
+/* What the routine leaves behind.  The last three rows and the two ids describe the LAST hit: ids 0xFFFFFFFF and those floats 0 when HitCount == 0.
+ * The minimum distance wins inside a step, and the triangle visited first in the reference's serial order keeps a tie. */
+typedef struct idkpt_sphere_collision {
+    float Position[3];          uint32_t HitCount;        /* the rewritten destination; recursive steps that hit */
+    float Velocity[3];          uint32_t TriangleId;      /* BlasDesc.TriangleOffset + the triangle's index in its BLAS */
+    float Center[3];            uint32_t BlasInstanceId;  /* movingSphere.Center on return */
+    float SlidingNormal[3];     float PenetrationDepth;   /* SceneHitInfo.SlidingPlane.Normal; bestPenetrationDepth */
+    float TriNormal[3];         float Distance;           /* SceneHitInfo.TriNormal; bestTriDistance */
+    float TriCollidingPoint[3]; uint32_t _pad;
+} idkpt_sphere_collision;
+IDKPT_STATIC_ASSERT(sizeof(idkpt_sphere_collision) == 96, "idkpt_sphere_collision");
+
 /* Everything the reference's PathTracer kernels read through fixed GL bindings
  * (Shaders/include/StaticStorageBuffers.glsl:9-173, StaticUniformBuffers.glsl:9-55), as explicit
  * host arrays owned by the caller: BVH.{BlasNodes,BlasTriangles,BlasesDesc,BlasInstances,TlasNodes}
@@ -198,10 +235,10 @@ typedef struct idkpt_stats {
 /* The layout above only ever GROWS at its end, and IDKPT_ABI_VERSION counts the growths (and every other change a host compiled against an older header could trip over: new
  * enum values of idkpt_buffer or idkpt_texture_format, new fields of idkpt_texture, new entry points: 5 = idkptComputeSky / idkptUpdateSky / idkptDownloadSky, 6 = idkptPresent / idkptDownloadDisplay / idkptGetDisplayDevicePtr,
  * 7 = idkptBloom / idkptGetBloomInfo / idkptDownloadBloom / idkptGetBloomDevicePtr, 8 = idkptUnprojectSky,
- * 9 = idkptSetPresentationSize / idkptGetPresentationSize / idkptGetBloomRoute / idkptGetBloomChainDevicePtr, 10 = idkptDownloadTileClasses).  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
+ * 9 = idkptSetPresentationSize / idkptGetPresentationSize / idkptGetBloomRoute / idkptGetBloomChainDevicePtr, 10 = idkptDownloadTileClasses, 11 = idkptCollideSpheres / idkptCollideSpheresDevice).  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
  * of ITS struct to idkptGetStatsSized and gets exactly that many bytes; idkptGetStats(ctx, out) is idkptGetStatsSized(ctx, out, sizeof(idkpt_stats)) of the header the LIBRARY
  * was built with — for hosts built from the same tree.  idkptGetAbiVersion() lets a host refuse a library older than the header it was written against. */
-#define IDKPT_ABI_VERSION 10
+#define IDKPT_ABI_VERSION 11
 
 /* ---- lifetime --------------------------------------------------------------------------- */
 /* new PathTracer(w,h,settings) (PathTracer.cs:170-212).  deviceCount = 1: the reference's situation, one GPU.
@@ -418,6 +455,14 @@ IDKPT_API int32_t idkptTraceShadows(idkpt_ctx* ctx, const idkpt_shadow_params* p
  * (whose time is mostly their PCIe copies: 64 B per ray, 16 B per pixel).  Single-device contexts only (IDKPT_ERR_INVALID_OPERATION otherwise). */
 IDKPT_API int32_t idkptTraceRaysDevice(idkpt_ctx* ctx, const idkpt_ray* dRays, size_t count, uint32_t flags, idkpt_hit* dHits);
 IDKPT_API int32_t idkptTraceShadowsDevice(idkpt_ctx* ctx, const idkpt_shadow_params* params, const float* dDepth, const float* dNormalOct, float* dVisibility);
+/* Moves `count` spheres through the scene: SceneVsMovingSphereCollisionRoutine per sphere, the whole routine (RecursiveSteps x TestSteps dependent box walks) on the
+ * device.  Sees the geometry of every scene update issued before it (idkptSkin, idkptRefitBlas, idkptUpdateBuffer, a TLAS build); never disturbs accumulation.
+ * idkptCollideSpheres: host pointers, synchronous; a multi-device context cuts the batch into one piece per member.  idkptCollideSpheresDevice: device pointers on the
+ * context's device (16-byte aligned, IDKPT_ERR_INVALID_ARGUMENT otherwise), no copies, asynchronous in stream order; single-device contexts only.  IDKPT_ERR_INVALID_OPERATION without a scene, or with UseTlas set and no TLAS
+ * nodes; IDKPT_ERR_INVALID_ARGUMENT for null pointers with count > 0, count >= 2^31, an unknown Response, TestSteps outside 1..64, RecursiveSteps outside 0..64 (the
+ * bounds keep one call from occupying the device for long) or a non-finite EpsilonNormalOffset.  count == 0 succeeds and touches nothing. */
+IDKPT_API int32_t idkptCollideSpheres(idkpt_ctx* ctx, const idkpt_collide_settings* settings, const idkpt_moving_sphere* spheres, size_t count, idkpt_sphere_collision* out);
+IDKPT_API int32_t idkptCollideSpheresDevice(idkpt_ctx* ctx, const idkpt_collide_settings* settings, const idkpt_moving_sphere* dSpheres, size_t count, idkpt_sphere_collision* dOut);
 /* Read back a scene buffer (tests: refit/skinning results). */
 IDKPT_API int32_t idkptDownloadBuffer(idkpt_ctx* ctx, int32_t which, size_t offsetBytes, size_t bytes, void* dst);
 
