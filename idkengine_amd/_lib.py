@@ -20,6 +20,7 @@ SYMBOLS = [
     "idkptBloom", "idkptGetBloomInfo", "idkptDownloadBloom", "idkptGetBloomDevicePtr",
     "idkptSetPresentationSize", "idkptGetPresentationSize", "idkptGetBloomRoute", "idkptGetBloomChainDevicePtr",
     "idkptCollideSpheres", "idkptCollideSpheresDevice",
+    "idkptDenoise", "idkptUploadDenoised", "idkptDownloadDenoised", "idkptGetDenoisedDevicePtr", "idkptGetDenoiseRoute", "idkptSetResultSource", "idkptGetResultSource",
 ]
 
 _lib = None
@@ -50,6 +51,8 @@ def load():
         "idkptBloom": [vp, i32, i32, vp], "idkptGetBloomInfo": [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)], "idkptDownloadBloom": [vp, i32, i32, i32, vp, sz], "idkptGetBloomDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(sz)],
         "idkptSetPresentationSize": [vp, i32, i32], "idkptGetPresentationSize": [vp, C.POINTER(i32), C.POINTER(i32)], "idkptGetBloomRoute": [vp, i32, C.POINTER(i32)], "idkptGetBloomChainDevicePtr": [vp, i32, i32, C.POINTER(vp), C.POINTER(sz)],
         "idkptCollideSpheres": [vp, vp, vp, sz, vp], "idkptCollideSpheresDevice": [vp, vp, vp, sz, vp],
+        "idkptDenoise": [vp, i32, vp], "idkptUploadDenoised": [vp, i32, vp, sz], "idkptDownloadDenoised": [vp, i32, vp, sz], "idkptGetDenoisedDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(sz)], "idkptGetDenoiseRoute": [vp, i32, i32, C.POINTER(i32)],
+        "idkptSetResultSource": [vp, i32], "idkptGetResultSource": [vp, C.POINTER(i32)],
         "idkptRefitBlas": [vp, i32], "idkptUploadUnskinnedVertices": [vp, vp, i32], "idkptSkin": [vp, u32, u32, u32, u32],
         "idkptDownloadBuffer": [vp, i32, sz, sz, vp], "idkptResetAccumulation": [vp], "idkptSetSampleSequence": [vp, u32, u32], "idkptGetAccumulatedSamples": [vp, C.POINTER(u32)],
         "idkptRender": [vp], "idkptSynchronize": [vp], "idkptDownload": [vp, i32, vp, sz], "idkptDownloadRays": [vp, vp, sz],

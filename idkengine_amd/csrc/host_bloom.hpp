@@ -44,6 +44,7 @@ static int32_t dev_Bloom(dev_ctx* ctx, int32_t slot, int32_t image, const idkpt_
     const int W = ctx->W, H = ctx->H, pw = pres_w(ctx), ph = pres_h(ctx);
     if (pw < 2 || ph < 2) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptBloom: the frame must be at least 2 x 2 (level 0 is width / 2 x height / 2)");
     if (slot < 0) slot = ctx->curSlot;
+    if (source_missing(ctx, image, slot)) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptBloom: the result source is IDKPT_RESULT_DENOISED and the slot holds no denoised image since the last resize (idkptDenoise / idkptUploadDenoised)");
     int w0 = 0, h0 = 0;
     const int levels = bloomt::bloom_levels(pw, ph, b->MinusLods, &w0, &h0);
     // a render size up to the presentation size (and the equal sizes of a context without one) always fits the staged tile; a larger one (supersampling) may not
@@ -61,8 +62,8 @@ static int32_t dev_Bloom(dev_ctx* ctx, int32_t slot, int32_t image, const idkpt_
     auto dim = [](int d0, int l) { return bloomt::level_dim(d0, l); };
     auto grid = [](int w, int h) { return dim3((unsigned)((w + bloomk::TILE - 1) / bloomk::TILE), (unsigned)((h + bloomk::TILE - 1) / bloomk::TILE)); };
     // down pass 0: the image, Lod 0, Prefilter -> down level 0
-    if (direct) hipLaunchKernelGGL(k_bloom_down0_direct, grid(w0, h0), dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, image, slot), W, H, lvl(s.down, 0), w0, h0, b->MaxColor, b->Threshold);
-    else hipLaunchKernelGGL(k_bloom_down0, grid(w0, h0), dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, image, slot), W, H, lvl(s.down, 0), w0, h0, b->MaxColor, b->Threshold);
+    if (direct) hipLaunchKernelGGL(k_bloom_down0_direct, grid(w0, h0), dim3(256), 0, ctx->stream, source_ptr(ctx, image, slot), W, H, lvl(s.down, 0), w0, h0, b->MaxColor, b->Threshold);
+    else hipLaunchKernelGGL(k_bloom_down0, grid(w0, h0), dim3(256), 0, ctx->stream, source_ptr(ctx, image, slot), W, H, lvl(s.down, 0), w0, h0, b->MaxColor, b->Threshold);
     // down pass l: down level l - 1 -> down level l; Lod = l - 1, so the pass that writes level 1 prefilters again (compute.glsl:41, Bloom.cs:85)
     for (int l = 1; l < levels; l++)
         hipLaunchKernelGGL((k_bloom_pass<0>), grid(dim(w0, l), dim(h0, l)), dim3(256), 0, ctx->stream, (const uint2*)lvl(s.down, l - 1), (const uint2*)nullptr, dim(w0, l - 1), dim(h0, l - 1), lvl(s.down, l), dim(w0, l), dim(h0, l), l == 1 ? 1 : 0, b->MaxColor, b->Threshold);

@@ -42,6 +42,15 @@ struct BloomSlot {
     void release() { down.release(); up.release(); out.release(); downBytes = upBytes = outBytes = 0; valid = false; }
 };
 
+// idkptDenoise / idkptUploadDenoised (host_denoise.hpp): the buffers of one ring slot — the denoised RGBA32F image and the two RGBA32F images the iterations alternate
+// between — and how the last idkptDenoise reached each iteration's taps
+struct DenoiseSlot {
+    DevBuf out, ping[2]; size_t outBytes = 0, pingBytes[2] = {0, 0};         // (bytes in front of each buffer's guard)
+    bool valid = false;                                                      // holds a denoised image (filtered or uploaded) since the last resize
+    int iterations = 0; uint8_t route[8] = {0};                              // of the last idkptDenoise (0 iterations: the image was uploaded); enum idkpt_denoise_route
+    void release() { out.release(); ping[0].release(); ping[1].release(); outBytes = pingBytes[0] = pingBytes[1] = 0; valid = false; iterations = 0; }
+};
+
 // Tuning / test options (idkptSetDeveloperOption; none is part of the reference's interface and results are bit-identical under all of them:
 // tests/test_gpu_worklist.py, test_gpu_layout.py).  The library itself never reads the environment; the Python host mirror forwards IDKPT_<NAME>.
 struct DevOptions {
@@ -190,6 +199,9 @@ struct dev_ctx {
     std::vector<DevBuf> disp; std::vector<int> dispFmt;   // idkptPresent: the display image of every ring slot (allocated at the first present of the slot) and its format (enum idkpt_display_format; -1: not presented since the last resize)
     std::vector<BloomSlot> bloom;   // idkptBloom: per ring slot, allocated at the slot's first bloom
     int presW = 0, presH = 0;       // idkptSetPresentationSize: the size of the display and bloom images (0, 0: the render size); a state of its own, kept by every resize
+    std::vector<DenoiseSlot> denoise;   // idkptDenoise / idkptUploadDenoised: per ring slot, allocated at the slot's first use
+    int resultSource = 0;               // idkptSetResultSource (enum idkpt_result_source): what IDKPT_IMAGE_RESULT means to idkptPresent and idkptBloom; a state of its own, kept by every resize
+    char* hDenoiseStage = nullptr; size_t hDenoiseStageBytes = 0; hipEvent_t evDenoiseStage = nullptr;   // pinned staging of idkptUploadDenoised's host image (the pattern of hSkyStage)
     DevBuf camTab;                                       // per-sample cameras of the batch being launched (ring mode)
     int rowLimit = 0x7fffffff;                           // idkptSetRowRange: at most this many local rows
     idkpt_bounce_exchange_fn exchangeFn = nullptr; void* exchangeUser = nullptr;   // exact multi-GPU deep paths (idkptSetBounceExchange)

@@ -36,6 +36,8 @@ static int alloc_frame_impl(dev_ctx* ctx)
     ctx->disp.clear(); ctx->dispFmt.clear();
     for (BloomSlot& s : ctx->bloom) s.release();                   // ... and so do the bloom chains (idkptBloom)
     ctx->bloom.clear();
+    for (DenoiseSlot& s : ctx->denoise) s.release();               // ... and the denoised images (idkptDenoise / idkptUploadDenoised)
+    ctx->denoise.clear();
     return IDKPT_OK;
 }
 
@@ -50,8 +52,9 @@ static int alloc_frame_keep_images(dev_ctx* ctx)
     for (int i = 0; i < 3; i++) { saved[i] = ctx->img[i]; ctx->img[i] = DevBuf(); }
     std::vector<DevBuf> disp; std::vector<int> dispFmt; disp.swap(ctx->disp); dispFmt.swap(ctx->dispFmt);   // (the display images stay as well: same size, same ring)
     std::vector<BloomSlot> bloom; bloom.swap(ctx->bloom);                                                   // (and the bloom chains)
+    std::vector<DenoiseSlot> denoise; denoise.swap(ctx->denoise);                                           // (and the denoised images)
     int rc = alloc_frame(ctx);
-    ctx->disp.swap(disp); ctx->dispFmt.swap(dispFmt); ctx->bloom.swap(bloom);
+    ctx->disp.swap(disp); ctx->dispFmt.swap(dispFmt); ctx->bloom.swap(bloom); ctx->denoise.swap(denoise);
     // The restore is ordered on the context's stream, behind the zero-fill alloc_frame_impl queued there: the stream is non-blocking, so
     // a null-stream copy would be unordered against that fill (the fill could land after the restore and wipe the accumulation).
     hipError_t e = hipSuccess;

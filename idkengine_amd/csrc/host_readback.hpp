@@ -223,6 +223,12 @@ static int32_t dev_GetPresentationSize(dev_ctx* ctx, int32_t* width, int32_t* he
     if (height) *height = pres_h(ctx);
     return IDKPT_OK;
 }
+// The result source (idkptSetResultSource; PathTracerPipeline.Result's switch): while it is DENOISED, IDKPT_IMAGE_RESULT means the slot's denoised image (host_denoise.hpp)
+// to idkptPresent and idkptBloom — and to nothing else.  source_missing: the call has to refuse (no denoised image in the slot since the last resize); source_ptr: the image
+// those two calls read.  Images 1 and 2 never look at the source.
+static bool source_denoised(const dev_ctx* ctx, int image) { return ctx->resultSource == IDKPT_RESULT_DENOISED && image == IDKPT_IMAGE_RESULT; }
+static bool source_missing(const dev_ctx* ctx, int image, int slot) { return source_denoised(ctx, image) && ((size_t)slot >= ctx->denoise.size() || !ctx->denoise[slot].valid); }
+static const float4* source_ptr(dev_ctx* ctx, int image, int slot) { return source_denoised(ctx, image) ? (const float4*)ctx->denoise[slot].out.p : image_ptr(ctx, image, slot); }
 // everything idkptPresent refuses before anything is launched (shared with the multi-device layer)
 static int32_t present_validate(dev_ctx* ctx, int32_t slot, int32_t image, const idkpt_tonemap* tm, int32_t format)
 {
@@ -241,6 +247,7 @@ static int32_t dev_Present(dev_ctx* ctx, int32_t slot, int32_t image, const idkp
     if (!ctx || !tm) return IDKPT_ERR_INVALID_ARGUMENT;
     { int rc = present_validate(ctx, slot, image, tm, format); if (rc) return rc; }
     if (slot < 0) slot = ctx->curSlot;
+    if (source_missing(ctx, image, slot)) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptPresent: the result source is IDKPT_RESULT_DENOISED and the slot holds no denoised image since the last resize (idkptDenoise / idkptUploadDenoised)");
     HIPC(hipSetDevice(ctx->device));
     FLUSH_KEEP();                                        // stream-ordered behind what was queued; the frame is complete without the deferred bounce's continuation (finish_deferred)
     { int rc = check_overflow(ctx); if (rc) return rc; }   // (no wait: see idkptGetFrameDevicePtr)
@@ -257,10 +264,10 @@ static int32_t dev_Present(dev_ctx* ctx, int32_t slot, int32_t image, const idkp
     if (scaled) { p.W = ctx->presW; p.rows = ctx->presH; }      // (the whole frame on this device: present_validate)
     const uint32_t threads = (uint32_t)(((size_t)p.W + 3) / 4 * p.rows);
     if (threads && scaled) {
-        with_flag(format == IDKPT_DISPLAY_RGBA32F, [&](auto F32) { launch(k_present_scaled<F32>, dim3((threads + 255u) / 256u), dim3(256), 0, ctx->stream, image_ptr(ctx, image, slot), ctx->W, ctx->H, (const float4*)dAdd0, (const float4*)dAdd1, buf.p, p); });
+        with_flag(format == IDKPT_DISPLAY_RGBA32F, [&](auto F32) { launch(k_present_scaled<F32>, dim3((threads + 255u) / 256u), dim3(256), 0, ctx->stream, source_ptr(ctx, image, slot), ctx->W, ctx->H, (const float4*)dAdd0, (const float4*)dAdd1, buf.p, p); });
         HIPC(hipGetLastError());
     } else if (threads) {
-        with_flag(format == IDKPT_DISPLAY_RGBA32F, [&](auto F32) { launch(k_present<F32>, dim3((threads + 255u) / 256u), dim3(256), 0, ctx->stream, image_ptr(ctx, image, slot), (const float4*)dAdd0, (const float4*)dAdd1, buf.p, p); });
+        with_flag(format == IDKPT_DISPLAY_RGBA32F, [&](auto F32) { launch(k_present<F32>, dim3((threads + 255u) / 256u), dim3(256), 0, ctx->stream, source_ptr(ctx, image, slot), (const float4*)dAdd0, (const float4*)dAdd1, buf.p, p); });
         HIPC(hipGetLastError());
     }
     ctx->dispFmt[slot] = format;

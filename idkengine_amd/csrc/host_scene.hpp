@@ -131,6 +131,9 @@ static int32_t dev_Destroy(dev_ctx* ctx)
     for (auto& t : ctx->texData) t.release();
     for (DevBuf& b : ctx->disp) b.release();
     for (BloomSlot& s : ctx->bloom) s.release();
+    for (DenoiseSlot& s : ctx->denoise) s.release();
+    if (ctx->hDenoiseStage) (void)hipHostFree(ctx->hDenoiseStage);
+    if (ctx->evDenoiseStage) (void)hipEventDestroy(ctx->evDenoiseStage);
     builder_scratch_free(ctx);
     if (ctx->hCounts) (void)hipHostFree(ctx->hCounts);
     if (ctx->hOverflow) (void)hipHostFree(ctx->hOverflow);

@@ -36,6 +36,7 @@ using namespace ptd;
 #include "kernels_sky.hpp"
 #include "kernels_unproject.hpp"
 #include "kernels_bloom.hpp"
+#include "kernels_denoise.hpp"
 #include "kernels_present.hpp"
 #include "bvh_gpu.hpp"
 #include "bvh_gpu_full.hpp"
@@ -52,6 +53,7 @@ using namespace ptd;
 #include "host_schedule.hpp"
 #include "host_readback.hpp"
 #include "host_bloom.hpp"
+#include "host_denoise.hpp"
 #include "host_options.hpp"
 #include "transport_rccl.hpp"
 

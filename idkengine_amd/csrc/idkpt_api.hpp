@@ -891,6 +891,24 @@ int32_t idkptGetBloomInfo(idkpt_ctx* c, int32_t slot, int32_t* levels, int32_t* 
 int32_t idkptDownloadBloom(idkpt_ctx* c, int32_t slot, int32_t chain, int32_t level, void* dst, size_t bytes) { BLOOM_ONE("idkptDownloadBloom", dev_DownloadBloom(m, slot, chain, level, dst, bytes)); }
 int32_t idkptGetBloomDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size_t* outBytes) { BLOOM_ONE("idkptGetBloomDevicePtr", dev_GetBloomDevicePtr(m, slot, outPtr, outBytes)); }
 
+// ---- the denoised image (host_denoise.hpp): one device, the whole frame — the taps of the last iteration reach 2 * 2^(Iterations - 1) rows
+#define DENOISE_ONE(who, call) do { if (!c) return IDKPT_ERR_INVALID_ARGUMENT; ONE(call); return gfail(c, IDKPT_ERR_INVALID_OPERATION, who ": the denoised image needs the whole frame on one device; a multi-device context has none"); } while (0)
+int32_t idkptDenoise(idkpt_ctx* c, int32_t slot, const idkpt_denoise* denoise) { DENOISE_ONE("idkptDenoise", dev_Denoise(m, slot, denoise)); }
+int32_t idkptUploadDenoised(idkpt_ctx* c, int32_t slot, const float* rgba, size_t bytes) { DENOISE_ONE("idkptUploadDenoised", dev_UploadDenoised(m, slot, rgba, bytes)); }
+int32_t idkptDownloadDenoised(idkpt_ctx* c, int32_t slot, float* rgba, size_t bytes) { DENOISE_ONE("idkptDownloadDenoised", dev_DownloadDenoised(m, slot, rgba, bytes)); }
+int32_t idkptGetDenoisedDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size_t* outBytes) { DENOISE_ONE("idkptGetDenoisedDevicePtr", dev_GetDenoisedDevicePtr(m, slot, outPtr, outBytes)); }
+int32_t idkptGetDenoiseRoute(idkpt_ctx* c, int32_t slot, int32_t iteration, int32_t* outRoute) { DENOISE_ONE("idkptGetDenoiseRoute", dev_GetDenoiseRoute(m, slot, iteration, outRoute)); }
+// the result source: a multi-device context stays at IDKPT_RESULT_NOISY (its members never look at anything else)
+int32_t idkptSetResultSource(idkpt_ctx* c, int32_t source)
+{
+    if (!c) return IDKPT_ERR_INVALID_ARGUMENT;
+    ONE(dev_SetResultSource(m, source));
+    GREQ(source == IDKPT_RESULT_NOISY || source == IDKPT_RESULT_DENOISED, "idkptSetResultSource: source must be IDKPT_RESULT_NOISY or IDKPT_RESULT_DENOISED");
+    if (source == IDKPT_RESULT_DENOISED) return gfail(c, IDKPT_ERR_INVALID_OPERATION, "idkptSetResultSource: the denoised image needs the whole frame on one device; a multi-device context has none");
+    return IDKPT_OK;
+}
+int32_t idkptGetResultSource(idkpt_ctx* c, int32_t* outSource) { if (!c || !outSource) return IDKPT_ERR_INVALID_ARGUMENT; return dev_GetResultSource(c->dev[0], outSource); }
+
 int32_t idkptResetAccumulation(idkpt_ctx* c) { if (!c) return IDKPT_ERR_INVALID_ARGUMENT; for (dev_ctx* m : c->dev) dev_ResetAccumulation(m); return IDKPT_OK; }
 int32_t idkptSetSampleSequence(idkpt_ctx* c, uint32_t first, uint32_t stride) { REPLICATE(SetSampleSequence, first, stride); }
 int32_t idkptGetAccumulatedSamples(idkpt_ctx* c, uint32_t* out) { if (!c || !out) return IDKPT_ERR_INVALID_ARGUMENT; return dev_GetAccumulatedSamples(c->dev[0], out); }

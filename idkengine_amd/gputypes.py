@@ -187,6 +187,19 @@ class BloomSettings(C.Structure):
         super().__init__(float(Threshold), float(MaxColor), int(MinusLods))
 
 
+IDKPT_RESULT_NOISY, IDKPT_RESULT_DENOISED = 0, 1           # enum idkpt_result_source (idkptSetResultSource): what image 0 means to idkptPresent and idkptBloom
+IDKPT_DENOISE_ROUTE_TILED, IDKPT_DENOISE_ROUTE_DIRECT = 0, 1   # enum idkpt_denoise_route (idkptGetDenoiseRoute): how an iteration reached its taps
+
+
+class Denoise(C.Structure):
+    """idkpt_denoise: the settings of idkptDenoise (include/idkpt.h, "denoised output"; no counterpart in the reference, whose denoiser is OIDN on the host).  The sigma
+    defaults are the tuned ones of profiles/denoise.md."""
+    _fields_ = [("Iterations", C.c_int32), ("ColorSigma", C.c_float), ("AlbedoSigma", C.c_float), ("NormalSigma", C.c_float), ("DemodulateAlbedo", C.c_int32)]
+
+    def __init__(self, Iterations=5, ColorSigma=8.0, AlbedoSigma=0.2, NormalSigma=0.5, DemodulateAlbedo=True):
+        super().__init__(int(Iterations), float(ColorSigma), float(AlbedoSigma), float(NormalSigma), int(DemodulateAlbedo))
+
+
 class Stats(C.Structure):
     _fields_ = [("RaysTraced", C.c_uint64), ("PrimaryRays", C.c_uint64), ("Frames", C.c_uint64),
                 ("LastAliveCounts", C.c_uint32 * 16), ("LastTraceMs", C.c_float), ("LastFrameMs", C.c_float),

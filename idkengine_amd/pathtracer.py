@@ -590,6 +590,54 @@ class PathTracer:
         self._check(self._L.idkptDownloadBloom(self._ctx, -1 if slot is None else int(slot), int(chain), int(level), out.ctypes.data, out.nbytes))
         return out
 
+    # ---- denoised output (idkptDenoise / idkptUploadDenoised / idkptDownloadDenoised / idkptSetResultSource): PathTracerPipeline.Result == Denoised
+    def Denoise(self, settings=None, slot=None):
+        """idkptDenoise + idkptDownloadDenoised: the edge-avoiding a-trous filter of include/idkpt.h over Result, guided by Albedo and Normal of ring slot `slot` (None: the
+        current one; needs OutputAOVs), as an (H, W, 4) float32 array (rgb, 1.0).  settings: a gputypes.Denoise; None = the tuned defaults.  The image stays in the slot:
+        with SetResultSource(IDKPT_RESULT_DENOISED), Present and Bloom read it in place of image 0.  Not OIDN and no approximation of it."""
+        if settings is None:
+            settings = T.Denoise()
+        if not isinstance(settings, T.Denoise):
+            raise TypeError("Denoise: settings must be a gputypes.Denoise")
+        slot = -1 if slot is None else int(slot)
+        self._check(self._L.idkptDenoise(self._ctx, slot, C.addressof(settings)))
+        return self.DownloadDenoised(slot)
+
+    def UploadDenoised(self, rgba, slot=None):
+        """idkptUploadDenoised: the host's own denoiser's output, an (H, W, 4) float32 array, becomes the denoised image of the slot (the reference's denoisedTexture.Upload2D)"""
+        rgba = np.ascontiguousarray(rgba, np.float32)
+        if rgba.shape != (self.height, self.width, 4):
+            raise ValueError(f"UploadDenoised: expected an array of shape {(self.height, self.width, 4)}, got {rgba.shape}")
+        self._check(self._L.idkptUploadDenoised(self._ctx, -1 if slot is None else int(slot), rgba.ctypes.data, rgba.nbytes))
+
+    def DownloadDenoised(self, slot=None):
+        """idkptDownloadDenoised: the denoised image of the slot, an (H, W, 4) float32 array"""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.idkptDownloadDenoised(self._ctx, -1 if slot is None else int(slot), out.ctypes.data, out.nbytes))
+        return out
+
+    def denoised_device_ptr(self, slot=None):
+        """idkptGetDenoisedDevicePtr: (device pointer, bytes) of the slot's denoised image, valid in stream order; 64 guard bytes follow"""
+        p = C.c_void_p(); n = C.c_size_t()
+        self._check(self._L.idkptGetDenoisedDevicePtr(self._ctx, -1 if slot is None else int(slot), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def denoise_route(self, iteration, slot=None):
+        """idkptGetDenoiseRoute: gputypes.IDKPT_DENOISE_ROUTE_TILED or IDKPT_DENOISE_ROUTE_DIRECT for an iteration of the slot's last Denoise"""
+        r = C.c_int32()
+        self._check(self._L.idkptGetDenoiseRoute(self._ctx, -1 if slot is None else int(slot), int(iteration), C.byref(r)))
+        return r.value
+
+    def SetResultSource(self, source):
+        """idkptSetResultSource: gputypes.IDKPT_RESULT_NOISY (default) or IDKPT_RESULT_DENOISED — what image 0 means to Present and Bloom (PathTracerPipeline.Result's switch).
+        A state of its own: ResetAccumulation does not revert it."""
+        self._check(self._L.idkptSetResultSource(self._ctx, int(source)))
+
+    def GetResultSource(self):
+        s = C.c_int32()
+        self._check(self._L.idkptGetResultSource(self._ctx, C.byref(s)))
+        return s.value
+
     def enable_counters(self, on=True):
         self._check(self._L.idkptEnableCounters(self._ctx, 1 if on else 0))
 

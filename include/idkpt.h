@@ -235,10 +235,11 @@ typedef struct idkpt_stats {
 /* The layout above only ever GROWS at its end, and IDKPT_ABI_VERSION counts the growths (and every other change a host compiled against an older header could trip over: new
  * enum values of idkpt_buffer or idkpt_texture_format, new fields of idkpt_texture, new entry points: 5 = idkptComputeSky / idkptUpdateSky / idkptDownloadSky, 6 = idkptPresent / idkptDownloadDisplay / idkptGetDisplayDevicePtr,
  * 7 = idkptBloom / idkptGetBloomInfo / idkptDownloadBloom / idkptGetBloomDevicePtr, 8 = idkptUnprojectSky,
- * 9 = idkptSetPresentationSize / idkptGetPresentationSize / idkptGetBloomRoute / idkptGetBloomChainDevicePtr, 10 = idkptDownloadTileClasses, 11 = idkptCollideSpheres / idkptCollideSpheresDevice).  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
+ * 9 = idkptSetPresentationSize / idkptGetPresentationSize / idkptGetBloomRoute / idkptGetBloomChainDevicePtr, 10 = idkptDownloadTileClasses, 11 = idkptCollideSpheres / idkptCollideSpheresDevice,
+ * 12 = idkptDenoise / idkptUploadDenoised / idkptDownloadDenoised / idkptGetDenoisedDevicePtr / idkptGetDenoiseRoute / idkptSetResultSource / idkptGetResultSource).  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
  * of ITS struct to idkptGetStatsSized and gets exactly that many bytes; idkptGetStats(ctx, out) is idkptGetStatsSized(ctx, out, sizeof(idkpt_stats)) of the header the LIBRARY
  * was built with — for hosts built from the same tree.  idkptGetAbiVersion() lets a host refuse a library older than the header it was written against. */
-#define IDKPT_ABI_VERSION 11
+#define IDKPT_ABI_VERSION 12
 
 /* ---- lifetime --------------------------------------------------------------------------- */
 /* new PathTracer(w,h,settings) (PathTracer.cs:170-212).  deviceCount = 1: the reference's situation, one GPU.
@@ -608,6 +609,71 @@ IDKPT_API int32_t idkptGetBloomRoute(idkpt_ctx* ctx, int32_t slot, int32_t* outR
  * is their sum, and the chain's 64 guard bytes of 0xA5 follow directly behind.  For hosts that sample a level themselves and for tests that look at the guard; does not wait:
  * valid in stream order (idkptGetStream) until the next bloom of that slot or resize.  Errors as idkptGetBloomDevicePtr; a wrong chain: IDKPT_ERR_INVALID_ARGUMENT. */
 IDKPT_API int32_t idkptGetBloomChainDevicePtr(idkpt_ctx* ctx, int32_t slot, int32_t chain, void** outPtr, size_t* outBytes);
+
+/* ---- denoised output (ABI 12): PathTracerPipeline.Result == Denoised (Source/Render/PathTracerPipeline.cs:13-67, Denoise(): 165-194) -------------------------------------
+ * The engine's displayed frame is PathTracerPipeline.Result, a switch over PathTracerOutput { Noisy, Denoised, Albedo, Normal }; Application.cs:215-223 feeds whatever
+ * it selects to Bloom.Compute and TonemapAndGamma.Compute.  Every ring slot can hold a DENOISED image of the render size (RGBA32F) beside its three accumulated ones, and
+ * there are two ways to fill it:
+ *   idkptUploadDenoised   the host's own denoiser's output (the reference runs OIDN on the CPU and calls denoisedTexture.Upload2D, PathTracerPipeline.cs:188);
+ *   idkptDenoise          a filter of this library, guided by the albedo and normal images the path tracer accumulates with OutputAOVs.
+ * idkptDenoise HAS NO COUNTERPART IN THE REFERENCE AND DOES NOT APPROXIMATE OIDN'S PICTURE: OIDN is a trained network (no weights, no network here: DESIGN.md section 8),
+ * this is the edge-avoiding a-trous wavelet filter (Dammertz, Sewtz, Hanika, Lensch 2010), the standard guided real-time denoiser — with one deliberate change: its range
+ * kernels are RATIONAL (Cauchy), 1 / (1 + |d|^2 / sigma^2), instead of Gaussian.  Every operation is then a correctly rounded binary32 + - * / (the library is compiled with
+ * -ffp-contract=off), so the result is defined BIT FOR BIT by the text below and checked against an independent numpy restatement (tests/denoise_ref.py).
+ *
+ * The filter.  c0 = Result.rgb, a = Albedo.rgb, n = Normal.rgb of the slot as accumulated (normals as stored, not renormalised); eps = 1e-3.
+ *   If DemodulateAlbedo: c0 = c0 / fmaxf(a, eps) per channel.
+ *   For i = 0 .. Iterations - 1, with s = 1 << i and c the previous iteration's output (c0 for i = 0), at every pixel p:
+ *     taps q = p + s * (dx, dy), dy the outer loop over -2 .. 2, dx the inner loop over -2 .. 2, all sums accumulated in that order; a tap outside the image is SKIPPED, not clamped;
+ *     h = k[dx + 2] * k[dy + 2], k = { 1/16, 1/4, 3/8, 1/4, 1/16 } (every product exact);
+ *     d(u) = u_q - u_p, |d|^2 = (d.x * d.x + d.y * d.y) + d.z * d.z;
+ *     w = ((h * (1 / (1 + |d(c)|^2 * invC_i))) * (1 / (1 + |d(a)|^2 * invA))) * (1 / (1 + |d(n)|^2 * invN));
+ *     invC_i = 1 / (sc * sc) with sc = ColorSigma * 2^-i (the colour sigma halves every iteration; the scaling is exact), invA = 1 / (AlbedoSigma * AlbedoSigma),
+ *     invN = 1 / (NormalSigma * NormalSigma), each computed once per launch on the host in binary32;
+ *     the tap contributes only if w > 0: sum += c_q * w per channel, sumW += w;
+ *     out = sum / sumW per channel; if sumW == 0, out = c_p unchanged.
+ *   After the last iteration, if DemodulateAlbedo: out = out * fmaxf(a, eps).  The stored alpha is 1.0.
+ * Non-finite values.  No texel value feeds an address.  `w > 0` is false for a NaN weight (a NaN or infinite texel or guide on either side of the difference) and for the
+ * zero weight of a difference whose square overflows, so a non-finite texel or guide contributes to no neighbour and every other pixel's value is what it would be with
+ * that tap outside the image.  A pixel that is NaN or infinite itself (colour or guide) drops every tap, its own included, and keeps its colour: sumW == 0.  A pixel whose
+ * squared differences to every neighbour overflow (FLT_MAX) keeps only its own tap, out = (c_p * h) / h with h = 9/64, its own colour to within one rounding per iteration.
+ * fmaxf makes a NaN albedo channel act as eps in the de- and remodulation.
+ *
+ * The calls behave as idkptBloom does: slot -1 is the current slot; queued samples are launched first; nothing but idkptDownloadDenoised waits for the GPU; the buffers
+ * (the denoised image and two RGBA32F images the iterations alternate between) belong to a ring slot, are allocated at the slot's first use — a context that never denoises
+ * allocates nothing —, are released by everything that re-makes the images (idkptSetSize, idkptSetFrameRing with another count, every row-layout call) and kept by
+ * idkptSetMaxBatch, idkptResetAccumulation, idkptBeginFrame and idkptSetPresentationSize: the denoised view "is not live", as the reference says — it is the picture of the
+ * moment it was made.  Each buffer ends with 64 guard bytes of 0xA5 that nothing writes.  idkptDenoise reads Result, Albedo and Normal and changes none of them, nor the
+ * accumulation.
+ * Scope: ONE device that holds the WHOLE frame (the taps of the last iteration reach 2 * 2^(Iterations - 1) rows).  A multi-device context, and a context that holds row
+ * bands or a strip, get IDKPT_ERR_INVALID_OPERATION from idkptDenoise, idkptUploadDenoised and idkptSetResultSource(IDKPT_RESULT_DENOISED).  idkptDenoise needs
+ * OutputAOVs != 0 in the current settings (the guides are not accumulated otherwise): IDKPT_ERR_INVALID_OPERATION without.  No size set: IDKPT_ERR_INVALID_OPERATION.
+ * Checked before anything is launched, IDKPT_ERR_INVALID_ARGUMENT: a slot outside the ring, Iterations outside 1..8, a sigma that is not finite and > 0, DemodulateAlbedo
+ * other than 0 / 1, `bytes` other than height * width * 16, a NULL pointer.  Reading a slot that holds no denoised image since the last resize: IDKPT_ERR_INVALID_OPERATION. */
+typedef struct idkpt_denoise {
+    int32_t Iterations;        /* 1..8; iteration i uses tap spacing 1 << i.  default 5 */
+    float   ColorSigma;        /* > 0, finite; on DEMODULATED radiance when DemodulateAlbedo; halves every iteration.  default 8.0 (tuned: profiles/denoise.md) */
+    float   AlbedoSigma;       /* > 0, finite.  default 0.2 */
+    float   NormalSigma;       /* > 0, finite.  default 0.5 */
+    int32_t DemodulateAlbedo;  /* 0 / 1.  default 1 */
+} idkpt_denoise;
+IDKPT_API int32_t idkptDenoise(idkpt_ctx* ctx, int32_t slot, const idkpt_denoise* denoise);               /* Result, Albedo, Normal of the slot -> its denoised image */
+IDKPT_API int32_t idkptUploadDenoised(idkpt_ctx* ctx, int32_t slot, const float* rgba, size_t bytes);     /* the host's own denoiser's output (Upload2D); bytes = height * width * 16; the array is borrowed for the call only */
+IDKPT_API int32_t idkptDownloadDenoised(idkpt_ctx* ctx, int32_t slot, float* rgba, size_t bytes);         /* synchronises like the other Download calls */
+IDKPT_API int32_t idkptGetDenoisedDevicePtr(idkpt_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes);   /* stream-ordered (idkptGetStream), does not wait; the guard bytes follow *outBytes */
+/* How iteration `iteration` of the slot's last idkptDenoise reached its taps (an observation for tests and profiles; both routes compute the same pixels bit for bit).
+ * IDKPT_ERR_INVALID_ARGUMENT for an iteration the last idkptDenoise of the slot did not run (an uploaded image ran none). */
+enum idkpt_denoise_route { IDKPT_DENOISE_ROUTE_TILED = 0 /* spacing 1, 2, 4: a 16 x 16 tile and its halo staged in LDS */, IDKPT_DENOISE_ROUTE_DIRECT = 1 /* spacing 8 and up: fetches from memory */ };
+IDKPT_API int32_t idkptGetDenoiseRoute(idkpt_ctx* ctx, int32_t slot, int32_t iteration, int32_t* outRoute);
+/* The PathTracerPipeline.Result getter.  While the source is IDKPT_RESULT_DENOISED, image == IDKPT_IMAGE_RESULT in idkptPresent and idkptBloom reads the slot's denoised
+ * image instead of the accumulated one — in those two calls only, and IDKPT_ERR_INVALID_OPERATION before anything is launched if the slot holds none since the last resize.
+ * Images 1 and 2 never look at the source; idkptDownload, idkptDownloadFrame, idkptGetFrameDevicePtr and idkptGetImageDevicePtr always return the accumulated images;
+ * enum idkpt_image does not grow (image 3 stays refused).  The default is IDKPT_RESULT_NOISY, under which nothing changes by a bit.  The source is a state of its own: kept
+ * by idkptSetSize, idkptSetFrameRing and idkptSetMaxBatch, and NOT reverted by idkptResetAccumulation — the engine's facade goes back to Noisy where it resets the
+ * accumulation (a moved camera invalidates the denoised picture); that line is the host's to write. */
+enum idkpt_result_source { IDKPT_RESULT_NOISY = 0, IDKPT_RESULT_DENOISED = 1 };
+IDKPT_API int32_t idkptSetResultSource(idkpt_ctx* ctx, int32_t source);
+IDKPT_API int32_t idkptGetResultSource(idkpt_ctx* ctx, int32_t* outSource);
 
 /* ---- render ----------------------------------------------------------------------------- */
 /* PathTracer.ResetAccumulation (PathTracer.cs:334-337) */
