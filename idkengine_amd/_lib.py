@@ -21,6 +21,7 @@ SYMBOLS = [
     "idkptSetPresentationSize", "idkptGetPresentationSize", "idkptGetBloomRoute", "idkptGetBloomChainDevicePtr",
     "idkptCollideSpheres", "idkptCollideSpheresDevice",
     "idkptDenoise", "idkptUploadDenoised", "idkptDownloadDenoised", "idkptGetDenoisedDevicePtr", "idkptGetDenoiseRoute", "idkptSetResultSource", "idkptGetResultSource",
+    "idkptSetNoiseEstimate", "idkptGetNoiseEstimate", "idkptEstimateNoise", "idkptDownloadNoise", "idkptGetNoiseDevicePtr", "idkptDownloadMoments", "idkptGetMomentsDevicePtr",
 ]
 
 _lib = None
@@ -53,6 +54,8 @@ def load():
         "idkptCollideSpheres": [vp, vp, vp, sz, vp], "idkptCollideSpheresDevice": [vp, vp, vp, sz, vp],
         "idkptDenoise": [vp, i32, vp], "idkptUploadDenoised": [vp, i32, vp, sz], "idkptDownloadDenoised": [vp, i32, vp, sz], "idkptGetDenoisedDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(sz)], "idkptGetDenoiseRoute": [vp, i32, i32, C.POINTER(i32)],
         "idkptSetResultSource": [vp, i32], "idkptGetResultSource": [vp, C.POINTER(i32)],
+        "idkptSetNoiseEstimate": [vp, i32], "idkptGetNoiseEstimate": [vp, C.POINTER(i32)], "idkptEstimateNoise": [vp, i32, vp], "idkptDownloadNoise": [vp, i32, vp, sz, vp],
+        "idkptGetNoiseDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(sz)], "idkptDownloadMoments": [vp, i32, vp, sz], "idkptGetMomentsDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(sz)],
         "idkptRefitBlas": [vp, i32], "idkptUploadUnskinnedVertices": [vp, vp, i32], "idkptSkin": [vp, u32, u32, u32, u32],
         "idkptDownloadBuffer": [vp, i32, sz, sz, vp], "idkptResetAccumulation": [vp], "idkptSetSampleSequence": [vp, u32, u32], "idkptGetAccumulatedSamples": [vp, C.POINTER(u32)],
         "idkptRender": [vp], "idkptSynchronize": [vp], "idkptDownload": [vp, i32, vp, sz], "idkptDownloadRays": [vp, vp, sz],

@@ -51,6 +51,13 @@ struct DenoiseSlot {
     void release() { out.release(); ping[0].release(); ping[1].release(); outBytes = pingBytes[0] = pingBytes[1] = 0; valid = false; iterations = 0; }
 };
 
+// idkptEstimateNoise (host_noise.hpp): the buffers of one ring slot — two floats (mean, max) per 8 x 8 tile and the idkpt_noise_summary record
+struct NoiseSlot {
+    DevBuf tiles, summary; size_t tileBytes = 0, summaryBytes = 0;           // (bytes in front of each buffer's guard)
+    int tilesX = 0, tilesY = 0; bool valid = false;                          // valid: holds an estimate since the last resize
+    void release() { tiles.release(); summary.release(); tileBytes = summaryBytes = 0; valid = false; }
+};
+
 // Tuning / test options (idkptSetDeveloperOption; none is part of the reference's interface and results are bit-identical under all of them:
 // tests/test_gpu_worklist.py, test_gpu_layout.py).  The library itself never reads the environment; the Python host mirror forwards IDKPT_<NAME>.
 struct DevOptions {
@@ -202,6 +209,9 @@ struct dev_ctx {
     std::vector<DenoiseSlot> denoise;   // idkptDenoise / idkptUploadDenoised: per ring slot, allocated at the slot's first use
     int resultSource = 0;               // idkptSetResultSource (enum idkpt_result_source): what IDKPT_IMAGE_RESULT means to idkptPresent and idkptBloom; a state of its own, kept by every resize
     char* hDenoiseStage = nullptr; size_t hDenoiseStageBytes = 0; hipEvent_t evDenoiseStage = nullptr;   // pinned staging of idkptUploadDenoised's host image (the pattern of hSkyStage)
+    int noiseOn = 0;                    // idkptSetNoiseEstimate: FinalDraw folds every sample's luminance into the moments images as well; a state of its own, kept by every resize
+    DevBuf noiseMom;                    // ... the moments images (m1, m2, 0, 1) of all ring slots, each followed by its guard bytes (host_noise.hpp); allocated at first use
+    std::vector<NoiseSlot> noise;       // idkptEstimateNoise: per ring slot, allocated at the slot's first estimate
     DevBuf camTab;                                       // per-sample cameras of the batch being launched (ring mode)
     int rowLimit = 0x7fffffff;                           // idkptSetRowRange: at most this many local rows
     idkpt_bounce_exchange_fn exchangeFn = nullptr; void* exchangeUser = nullptr;   // exact multi-GPU deep paths (idkptSetBounceExchange)

@@ -38,6 +38,10 @@ static int alloc_frame_impl(dev_ctx* ctx)
     ctx->bloom.clear();
     for (DenoiseSlot& s : ctx->denoise) s.release();               // ... and the denoised images (idkptDenoise / idkptUploadDenoised)
     ctx->denoise.clear();
+    ctx->noiseMom.release();                                       // ... the moments images (idkptSetNoiseEstimate; zeroed again at their next use) and the estimates made of them
+    for (NoiseSlot& s : ctx->noise) s.release();
+    ctx->noise.clear();
+    if (ctx->grouped || ctx->rowMod != 1 || ctx->rowRem != 0 || ctx->rows != ctx->H) ctx->noiseOn = 0;   // a shard of the rows: the estimate needs the whole frame (host_noise.hpp)
     return IDKPT_OK;
 }
 
@@ -53,8 +57,9 @@ static int alloc_frame_keep_images(dev_ctx* ctx)
     std::vector<DevBuf> disp; std::vector<int> dispFmt; disp.swap(ctx->disp); dispFmt.swap(ctx->dispFmt);   // (the display images stay as well: same size, same ring)
     std::vector<BloomSlot> bloom; bloom.swap(ctx->bloom);                                                   // (and the bloom chains)
     std::vector<DenoiseSlot> denoise; denoise.swap(ctx->denoise);                                           // (and the denoised images)
+    DevBuf noiseMom = ctx->noiseMom; ctx->noiseMom = DevBuf(); std::vector<NoiseSlot> noise; noise.swap(ctx->noise);   // (and the moments images with their estimates)
     int rc = alloc_frame(ctx);
-    ctx->disp.swap(disp); ctx->dispFmt.swap(dispFmt); ctx->bloom.swap(bloom); ctx->denoise.swap(denoise);
+    ctx->disp.swap(disp); ctx->dispFmt.swap(dispFmt); ctx->bloom.swap(bloom); ctx->denoise.swap(denoise); ctx->noiseMom = noiseMom; ctx->noise.swap(noise);
     // The restore is ordered on the context's stream, behind the zero-fill alloc_frame_impl queued there: the stream is non-blocking, so
     // a null-stream copy would be unordered against that fill (the fill could land after the restore and wipe the accumulation).
     hipError_t e = hipSuccess;

@@ -132,6 +132,8 @@ static int32_t dev_Destroy(dev_ctx* ctx)
     for (DevBuf& b : ctx->disp) b.release();
     for (BloomSlot& s : ctx->bloom) s.release();
     for (DenoiseSlot& s : ctx->denoise) s.release();
+    ctx->noiseMom.release();
+    for (NoiseSlot& s : ctx->noise) s.release();
     if (ctx->hDenoiseStage) (void)hipHostFree(ctx->hDenoiseStage);
     if (ctx->evDenoiseStage) (void)hipEventDestroy(ctx->evDenoiseStage);
     builder_scratch_free(ctx);

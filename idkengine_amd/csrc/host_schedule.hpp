@@ -374,11 +374,16 @@ static int defer_last_bounce(Batch& b, int j, const uint32_t* q, const uint32_t*
     return IDKPT_OK;
 }
 
+static int noise_moments_ensure(dev_ctx* ctx); static float4* noise_moments_ptr(dev_ctx* ctx, int slot); static size_t noise_mom_stride(const dev_ctx* ctx);   // (host_noise.hpp)
 // FinalDraw (which also resets the batch counters for the next batch) and what the context remembers of the batch
 static int final_draw(Batch& b)
 {
     dev_ctx* ctx = b.ctx; hipStream_t st = b.st;
     ctx->lastQueueSide = b.side; ctx->lastQueueCountSlot = b.depth; ctx->lastFast = b.fast; ctx->lastNeedsRegen = b.fast; ctx->lastTileClass = b.tileClass != nullptr; ctx->lastBatch = b.B; ctx->lastFrame = b.f;
+    if (ctx->noiseOn) {                                  // idkptSetNoiseEstimate: the sibling kernel folds the luminance moments in the same loop (one device, whole frame: host_noise.hpp)
+        launch(k_final_draw_noise, dim3((b.N + 255) / 256), dim3(256), 0, st, b.s, b.f, b.rays, image_ptr(ctx, 0, 0), image_ptr(ctx, 1, 0), image_ptr(ctx, 2, 0), b.N, b.tileClass, b.work, (uint32_t)WORK_WORDS, b.counts, (uint32_t)MAX_DEPTH_SLOTS,
+               noise_moments_ptr(ctx, 0), noise_mom_stride(ctx));
+    } else
     launch(k_final_draw, dim3((b.N + 255) / 256), dim3(256), 0, st, b.s, b.f, b.rays, image_ptr(ctx, 0, 0), image_ptr(ctx, 1, 0), image_ptr(ctx, 2, 0), b.N, b.tileClass, b.work, (uint32_t)WORK_WORDS, b.counts, (uint32_t)MAX_DEPTH_SLOTS);
     HIPC(hipGetLastError()); ctx->countersDirty = false;
     graph_probe_end(b);
@@ -397,6 +402,7 @@ static int flush_batch(dev_ctx* ctx)
 {
     if (ctx->pending.empty()) return IDKPT_OK;
     if (ctx->grouped && !ctx->inGroupFlush) return fail(ctx, IDKPT_ERR_UNKNOWN, "internal: a member of a multi-device context was flushed on its own");
+    if (ctx->noiseOn) { int rc = noise_moments_ensure(ctx); if (rc) return rc; }   // (the moments images FinalDraw folds into: allocated and zeroed at their first batch)
     Batch b; batch_views(ctx, b, (int)ctx->pending.size(), ctx->Npad); int rc;
     if ((rc = stage_versions_cameras(b))) return rc;
     if ((rc = frame_setup(b))) return rc;

@@ -37,6 +37,7 @@ using namespace ptd;
 #include "kernels_unproject.hpp"
 #include "kernels_bloom.hpp"
 #include "kernels_denoise.hpp"
+#include "kernels_noise.hpp"
 #include "kernels_present.hpp"
 #include "bvh_gpu.hpp"
 #include "bvh_gpu_full.hpp"
@@ -54,6 +55,7 @@ using namespace ptd;
 #include "host_readback.hpp"
 #include "host_bloom.hpp"
 #include "host_denoise.hpp"
+#include "host_noise.hpp"
 #include "host_options.hpp"
 #include "transport_rccl.hpp"
 

@@ -909,6 +909,23 @@ int32_t idkptSetResultSource(idkpt_ctx* c, int32_t source)
 }
 int32_t idkptGetResultSource(idkpt_ctx* c, int32_t* outSource) { if (!c || !outSource) return IDKPT_ERR_INVALID_ARGUMENT; return dev_GetResultSource(c->dev[0], outSource); }
 
+// ---- the noise estimate (host_noise.hpp): one device, the whole frame — a tile's moments live where its rows are.  A multi-device context stays switched off (its members never fold)
+#define NOISE_ONE(who, call) do { if (!c) return IDKPT_ERR_INVALID_ARGUMENT; ONE(call); return gfail(c, IDKPT_ERR_INVALID_OPERATION, who ": the noise estimate needs the whole frame on one device; a multi-device context has none"); } while (0)
+int32_t idkptSetNoiseEstimate(idkpt_ctx* c, int32_t enable)
+{
+    if (!c) return IDKPT_ERR_INVALID_ARGUMENT;
+    ONE(dev_SetNoiseEstimate(m, enable));
+    GREQ(enable == 0 || enable == 1, "idkptSetNoiseEstimate: enable must be 0 or 1");
+    if (enable) return gfail(c, IDKPT_ERR_INVALID_OPERATION, "idkptSetNoiseEstimate: the noise estimate needs the whole frame on one device; a multi-device context has none");
+    return IDKPT_OK;
+}
+int32_t idkptGetNoiseEstimate(idkpt_ctx* c, int32_t* outEnable) { if (!c || !outEnable) return IDKPT_ERR_INVALID_ARGUMENT; return dev_GetNoiseEstimate(c->dev[0], outEnable); }
+int32_t idkptEstimateNoise(idkpt_ctx* c, int32_t slot, const idkpt_noise* noise) { NOISE_ONE("idkptEstimateNoise", dev_EstimateNoise(m, slot, noise)); }
+int32_t idkptDownloadNoise(idkpt_ctx* c, int32_t slot, float* tiles, size_t bytes, idkpt_noise_summary* outSummary) { NOISE_ONE("idkptDownloadNoise", dev_DownloadNoise(m, slot, tiles, bytes, outSummary)); }
+int32_t idkptGetNoiseDevicePtr(idkpt_ctx* c, int32_t slot, void** outTiles, void** outSummary, size_t* outTileBytes) { NOISE_ONE("idkptGetNoiseDevicePtr", dev_GetNoiseDevicePtr(m, slot, outTiles, outSummary, outTileBytes)); }
+int32_t idkptDownloadMoments(idkpt_ctx* c, int32_t slot, float* rgba, size_t bytes) { NOISE_ONE("idkptDownloadMoments", dev_DownloadMoments(m, slot, rgba, bytes)); }
+int32_t idkptGetMomentsDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size_t* outBytes) { NOISE_ONE("idkptGetMomentsDevicePtr", dev_GetMomentsDevicePtr(m, slot, outPtr, outBytes)); }
+
 int32_t idkptResetAccumulation(idkpt_ctx* c) { if (!c) return IDKPT_ERR_INVALID_ARGUMENT; for (dev_ctx* m : c->dev) dev_ResetAccumulation(m); return IDKPT_OK; }
 int32_t idkptSetSampleSequence(idkpt_ctx* c, uint32_t first, uint32_t stride) { REPLICATE(SetSampleSequence, first, stride); }
 int32_t idkptGetAccumulatedSamples(idkpt_ctx* c, uint32_t* out) { if (!c || !out) return IDKPT_ERR_INVALID_ARGUMENT; return dev_GetAccumulatedSamples(c->dev[0], out); }

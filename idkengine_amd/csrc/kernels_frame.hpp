@@ -1,6 +1,7 @@
 // kernels_frame.hpp — FinalDraw, ray-state completion for idkptDownloadRays, miss pre-fill, derived triangle layout.
 // Part of the single translation unit idkpt.hip (included there, in this order); see DESIGN.md §4 for the kernel table.
 #pragma once
+#include "noise_texel.hpp"
 
 // FinalDraw/compute.glsl:24-62
 DEV f3 TurboColormap(float x)
@@ -13,20 +14,21 @@ DEV f3 TurboColormap(float x)
     float b = (((v0 * 0.10667330f + v1 * 12.64194608f) + v2 * -60.58204836f) + v3 * 110.36276771f) + (w0 * -89.90310912f + w1 * 27.34824973f);
     return mk3(r, g, b);
 }
-__global__ __launch_bounds__(256) void k_final_draw(DScene s, Frame f, RayBufs rays, float4* imgResult, float4* imgAlbedo, float4* imgNormal, uint32_t N, const uint8_t* tileClass,
-                                                    uint32_t* zeroWork, uint32_t nWork, uint32_t* zeroCounts, uint32_t nCounts)
+// The body of FinalDraw, written once for its two kernels (which reset the batch counters and name the pixel i < N).  NOISE (idkptSetNoiseEstimate, include/idkpt.h "noise estimate"): the luminance of every value folded into Result
+// is folded, with the same weight, into the slot's moments image (m1, m2, 0, 1) as well (noise_texel.hpp) — the per-sample radiance is gone after this loop, so this is the
+// one place a variance can come from.  The moments image of ring slot q starts at q * momStride (its guard bytes lie between the slots).  Nothing of NOISE touches r, ra, rn.
+template <bool NOISE>
+__device__ __forceinline__ void final_draw_body(const DScene& s, const Frame& f, const RayBufs& rays, float4* imgResult, float4* imgAlbedo, float4* imgNormal, uint32_t N, const uint8_t* tileClass,
+                                                uint32_t i, float4* imgMoments, size_t momStride)
 {
-    // last kernel of a batch: nothing reads this batch's work-list and queue-length counters any more, so they are reset here for the next batch
-    // (two memset launches per batch less: they were 5 % of a frame that is rendered alone)
-    if (blockIdx.x == 0) { for (uint32_t k = threadIdx.x; k < nWork; k += blockDim.x) zeroWork[k] = 0u; for (uint32_t k = threadIdx.x; k < nCounts; k += blockDim.x) zeroCounts[k] = 0u; }
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= N) return;
     // the images of ring slot q start at q*N; samples are accumulated in submission order, exactly like consecutive FinalDraw dispatches,
     // each into the image of its own frame (consecutive samples of one frame share a slot)
     uint32_t slot = f.slotOf[0];
     float4 o = imgResult[(size_t)slot * N + i];
     f3 r = mk3(o.x, o.y, o.z), ra = splat3(0.0f), rn = splat3(0.0f);
     if (f.outputAovs) { float4 oa = imgAlbedo[(size_t)slot * N + i], on = imgNormal[(size_t)slot * N + i]; ra = mk3(oa.x, oa.y, oa.z); rn = mk3(on.x, on.y, on.z); }
+    float m1 = 0.0f, m2 = 0.0f;
+    if constexpr (NOISE) { const float4 om = imgMoments[(size_t)slot * momStride + i]; m1 = om.x; m2 = om.y; }
     const uint32_t px = i % (uint32_t)f.W, py = i / (uint32_t)f.W, tilesX = ((uint32_t)f.W + 7) / 8;
     const uint32_t tile = (py >> 3) * tilesX + (px >> 3), nTilesAll = tilesX * (((uint32_t)f.rows + 7) / 8);
     const uint32_t sharedCls = (tileClass && !f.tilePerSample) ? tileClass[tile] : 0u;   // one camera and one scene version for the whole batch: one lookup
@@ -34,9 +36,11 @@ __global__ __launch_bounds__(256) void k_final_draw(DScene s, Frame f, RayBufs r
         if (f.slotOf[k] != slot) {                       // next frame of the ring: store, switch, load
             imgResult[(size_t)slot * N + i] = make_float4(r.x, r.y, r.z, 1.0f);
             if (f.outputAovs) { imgAlbedo[(size_t)slot * N + i] = make_float4(ra.x, ra.y, ra.z, 1.0f); imgNormal[(size_t)slot * N + i] = make_float4(rn.x, rn.y, rn.z, 1.0f); }
+            if constexpr (NOISE) imgMoments[(size_t)slot * momStride + i] = make_float4(m1, m2, 0.0f, 1.0f);
             slot = f.slotOf[k];
             o = imgResult[(size_t)slot * N + i]; r = mk3(o.x, o.y, o.z);
             if (f.outputAovs) { float4 oa = imgAlbedo[(size_t)slot * N + i], on = imgNormal[(size_t)slot * N + i]; ra = mk3(oa.x, oa.y, oa.z); rn = mk3(on.x, on.y, on.z); }
+            if constexpr (NOISE) { const float4 om = imgMoments[(size_t)slot * momStride + i]; m1 = om.x; m2 = om.y; }
         }
         const size_t rid = (size_t)k * f.Npad + i;
         float w = 1.0f / ((float)f.accum[k] + 1.0f);
@@ -53,10 +57,31 @@ __global__ __launch_bounds__(256) void k_final_draw(DScene s, Frame f, RayBufs r
         }
         if (f.g.DoDebugBVHTraversal) nr = TurboColormap(rays.o_ior[rid].w / 150.0f);
         r = gmix(r, nr, w);
+        if constexpr (NOISE) noiset::fold(&m1, &m2, noiset::luminance(nr.x, nr.y, nr.z), w);
         if (f.outputAovs) { float4 a = rays.aovA[rid], n = rays.aovN[rid]; ra = gmix(ra, mk3(a.x, a.y, a.z), w); rn = gmix(rn, mk3(n.x, n.y, n.z), w); }
     }
     imgResult[(size_t)slot * N + i] = make_float4(r.x, r.y, r.z, 1.0f);
     if (f.outputAovs) { imgAlbedo[(size_t)slot * N + i] = make_float4(ra.x, ra.y, ra.z, 1.0f); imgNormal[(size_t)slot * N + i] = make_float4(rn.x, rn.y, rn.z, 1.0f); }
+    if constexpr (NOISE) imgMoments[(size_t)slot * momStride + i] = make_float4(m1, m2, 0.0f, 1.0f);
+}
+__global__ __launch_bounds__(256) void k_final_draw(DScene s, Frame f, RayBufs rays, float4* imgResult, float4* imgAlbedo, float4* imgNormal, uint32_t N, const uint8_t* tileClass,
+                                                    uint32_t* zeroWork, uint32_t nWork, uint32_t* zeroCounts, uint32_t nCounts)
+{
+    // last kernel of a batch: nothing reads this batch's work-list and queue-length counters any more, so they are reset here for the next batch
+    // (two memset launches per batch less: they were 5 % of a frame that is rendered alone)
+    if (blockIdx.x == 0) { for (uint32_t k = threadIdx.x; k < nWork; k += blockDim.x) zeroWork[k] = 0u; for (uint32_t k = threadIdx.x; k < nCounts; k += blockDim.x) zeroCounts[k] = 0u; }
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    final_draw_body<false>(s, f, rays, imgResult, imgAlbedo, imgNormal, N, tileClass, i, nullptr, 0);
+}
+// the same with the moments image (the switch of idkptSetNoiseEstimate is on): 32 B more per pixel read and written
+__global__ __launch_bounds__(256) void k_final_draw_noise(DScene s, Frame f, RayBufs rays, float4* imgResult, float4* imgAlbedo, float4* imgNormal, uint32_t N, const uint8_t* tileClass,
+                                                          uint32_t* zeroWork, uint32_t nWork, uint32_t* zeroCounts, uint32_t nCounts, float4* imgMoments, size_t momStride)
+{
+    if (blockIdx.x == 0) { for (uint32_t k = threadIdx.x; k < nWork; k += blockDim.x) zeroWork[k] = 0u; for (uint32_t k = threadIdx.x; k < nCounts; k += blockDim.x) zeroCounts[k] = 0u; }   // (as k_final_draw)
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    final_draw_body<true>(s, f, rays, imgResult, imgAlbedo, imgNormal, N, tileClass, i, imgMoments, momStride);
 }
 
 // idkptDownloadRays support: the ray-state planes k_gen_primary skipped for culled pixels (flag 2) of one sample of the batch

@@ -200,6 +200,20 @@ class Denoise(C.Structure):
         super().__init__(int(Iterations), float(ColorSigma), float(AlbedoSigma), float(NormalSigma), int(DemodulateAlbedo))
 
 
+class Noise(C.Structure):
+    """idkpt_noise: the settings of idkptEstimateNoise (include/idkpt.h, "noise estimate"; no counterpart in the reference).  The defaults are starting values nobody has
+    tuned (profiles/noise.md)."""
+    _fields_ = [("Epsilon", C.c_float), ("Threshold", C.c_float)]
+
+    def __init__(self, Epsilon=1e-2, Threshold=0.05):
+        super().__init__(float(Epsilon), float(Threshold))
+
+
+class NoiseSummary(C.Structure):
+    """idkpt_noise_summary: what idkptEstimateNoise leaves beside the tile map"""
+    _fields_ = [("TilesAbove", C.c_uint32), ("MaxTileMean", C.c_float), ("Tiles", C.c_uint32), ("Samples", C.c_uint32)]
+
+
 class Stats(C.Structure):
     _fields_ = [("RaysTraced", C.c_uint64), ("PrimaryRays", C.c_uint64), ("Frames", C.c_uint64),
                 ("LastAliveCounts", C.c_uint32 * 16), ("LastTraceMs", C.c_float), ("LastFrameMs", C.c_float),

@@ -638,6 +638,53 @@ class PathTracer:
         self._check(self._L.idkptGetResultSource(self._ctx, C.byref(s)))
         return s.value
 
+    # ---- noise estimate (idkptSetNoiseEstimate / idkptEstimateNoise / idkptDownloadNoise / idkptDownloadMoments): no counterpart in the reference
+    def SetNoiseEstimate(self, enable):
+        """idkptSetNoiseEstimate: while on, FinalDraw keeps the luminance moments (m1, m2) of every pixel beside the running mean.  Changing the value launches the queued
+        samples and restarts the accumulation.  One device that holds the whole frame."""
+        self._check(self._L.idkptSetNoiseEstimate(self._ctx, 1 if enable else 0))
+
+    def GetNoiseEstimate(self):
+        e = C.c_int32()
+        self._check(self._L.idkptGetNoiseEstimate(self._ctx, C.byref(e)))
+        return bool(e.value)
+
+    def EstimateNoise(self, settings=None, slot=None):
+        """idkptEstimateNoise + idkptDownloadNoise: the relative standard error of the mean luminance per 8 x 8 tile of ring slot `slot` (None: the current one) as a
+        (tilesY, tilesX, 2) float32 array of (mean, max), and the summary as a dict.  settings: a gputypes.Noise; None = the (untuned) defaults.  Needs 2 samples."""
+        if settings is None:
+            settings = T.Noise()
+        if not isinstance(settings, T.Noise):
+            raise TypeError("EstimateNoise: settings must be a gputypes.Noise")
+        slot = -1 if slot is None else int(slot)
+        self._check(self._L.idkptEstimateNoise(self._ctx, slot, C.addressof(settings)))
+        return self.DownloadNoise(slot)
+
+    def DownloadNoise(self, slot=None):
+        """idkptDownloadNoise: (tiles, summary) of the slot's last EstimateNoise"""
+        tiles = np.zeros(((self.height + 7) // 8, (self.width + 7) // 8, 2), np.float32)
+        s = T.NoiseSummary()
+        self._check(self._L.idkptDownloadNoise(self._ctx, -1 if slot is None else int(slot), tiles.ctypes.data, tiles.nbytes, C.addressof(s)))
+        return tiles, {"TilesAbove": s.TilesAbove, "MaxTileMean": s.MaxTileMean, "Tiles": s.Tiles, "Samples": s.Samples}
+
+    def DownloadMoments(self, slot=None):
+        """idkptDownloadMoments: the moments image of the slot, an (H, W, 4) float32 array of (m1, m2, 0, 1)"""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.idkptDownloadMoments(self._ctx, -1 if slot is None else int(slot), out.ctypes.data, out.nbytes))
+        return out
+
+    def noise_device_ptrs(self, slot=None):
+        """idkptGetNoiseDevicePtr: (tile map pointer, summary pointer, tile map bytes), valid in stream order; 64 guard bytes follow each"""
+        t = C.c_void_p(); s = C.c_void_p(); n = C.c_size_t()
+        self._check(self._L.idkptGetNoiseDevicePtr(self._ctx, -1 if slot is None else int(slot), C.byref(t), C.byref(s), C.byref(n)))
+        return t.value, s.value, n.value
+
+    def moments_device_ptr(self, slot=None):
+        """idkptGetMomentsDevicePtr: (device pointer, bytes) of the slot's moments image, valid in stream order; 64 guard bytes follow"""
+        p = C.c_void_p(); n = C.c_size_t()
+        self._check(self._L.idkptGetMomentsDevicePtr(self._ctx, -1 if slot is None else int(slot), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
     def enable_counters(self, on=True):
         self._check(self._L.idkptEnableCounters(self._ctx, 1 if on else 0))
 

@@ -236,7 +236,8 @@ typedef struct idkpt_stats {
  * enum values of idkpt_buffer or idkpt_texture_format, new fields of idkpt_texture, new entry points: 5 = idkptComputeSky / idkptUpdateSky / idkptDownloadSky, 6 = idkptPresent / idkptDownloadDisplay / idkptGetDisplayDevicePtr,
  * 7 = idkptBloom / idkptGetBloomInfo / idkptDownloadBloom / idkptGetBloomDevicePtr, 8 = idkptUnprojectSky,
  * 9 = idkptSetPresentationSize / idkptGetPresentationSize / idkptGetBloomRoute / idkptGetBloomChainDevicePtr, 10 = idkptDownloadTileClasses, 11 = idkptCollideSpheres / idkptCollideSpheresDevice,
- * 12 = idkptDenoise / idkptUploadDenoised / idkptDownloadDenoised / idkptGetDenoisedDevicePtr / idkptGetDenoiseRoute / idkptSetResultSource / idkptGetResultSource).  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
+ * 12 = idkptDenoise / idkptUploadDenoised / idkptDownloadDenoised / idkptGetDenoisedDevicePtr / idkptGetDenoiseRoute / idkptSetResultSource / idkptGetResultSource).  The noise-estimate entry points (idkptSetNoiseEstimate ... idkptGetMomentsDevicePtr, below) were added WITHOUT a new number: nothing a host of ABI 12 can
+ * trip over changed, and a host that wants them looks the symbols up (dlsym / GetProcAddress: a library without them has none of the seven).  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
  * of ITS struct to idkptGetStatsSized and gets exactly that many bytes; idkptGetStats(ctx, out) is idkptGetStatsSized(ctx, out, sizeof(idkpt_stats)) of the header the LIBRARY
  * was built with — for hosts built from the same tree.  idkptGetAbiVersion() lets a host refuse a library older than the header it was written against. */
 #define IDKPT_ABI_VERSION 12
@@ -674,6 +675,70 @@ IDKPT_API int32_t idkptGetDenoiseRoute(idkpt_ctx* ctx, int32_t slot, int32_t ite
 enum idkpt_result_source { IDKPT_RESULT_NOISY = 0, IDKPT_RESULT_DENOISED = 1 };
 IDKPT_API int32_t idkptSetResultSource(idkpt_ctx* ctx, int32_t source);
 IDKPT_API int32_t idkptGetResultSource(idkpt_ctx* ctx, int32_t* outSource);
+
+/* ---- noise estimate (added under ABI 12; detect by symbol): how converged is the frame, and where is it not --------------------------------------------------------------------------------------------
+ * THIS HAS NO COUNTERPART IN THE REFERENCE.  The engine decides "denoise now" by a fixed sample count (AutoDenoiseSamplesThreshold, PathTracerPipeline.cs); a host of this
+ * library sees the sample count and nothing else, and after FinalDraw's fold the per-sample radiance is gone, so no later pass can recover a variance.  With the switch
+ * below ON, FinalDraw keeps the first two moments of every pixel's luminance beside the running mean, and idkptEstimateNoise turns them into a relative standard error per
+ * 8 x 8 tile (the first-hit stage's tile grid) and a four-word summary: enough for a host to decide when a frame is worth denoising or presenting and which tiles are still
+ * noisy.  Every operation is a correctly rounded binary32 + - * / or sqrt in the written order (-ffp-contract=off), so the text below defines the result BIT FOR BIT; it is
+ * checked against an independent numpy restatement (tests/noise_ref.py).  Nothing here changes what Result, Albedo or Normal hold, by a bit, on or off.
+ *
+ * The switch.  idkptSetNoiseEstimate(ctx, enable), enable 0 / 1, default 0.  Under 0 nothing is allocated and the kernels launched are the ones of a library without this
+ * section.  CHANGING the value launches the queued samples first and then restarts the accumulation of every ring slot (idkptGetAccumulatedSamples returns 0), as
+ * idkptSetSampleSequence does: moments and images always count the same samples.  Setting the value it already has changes nothing.  The switch is a state of its own, kept
+ * by idkptSetSize, idkptSetFrameRing and idkptSetMaxBatch.  Scope: ONE device that holds the WHOLE frame (the scope of idkptDenoise).  A multi-device context, and a context
+ * that holds row bands or a strip, get IDKPT_ERR_INVALID_OPERATION when enabling; a row-layout call that leaves a context with a shard of the rows turns the switch off.
+ *
+ * The moments image.  While the switch is on every ring slot owns one more RGBA32F image of the render size holding (m1, m2, 0, 1), allocated zeroed at first use, followed by
+ * 64 guard bytes of 0xA5 that nothing writes; released by everything that re-makes the images (idkptSetSize, idkptSetFrameRing with another count, every row-layout call) and
+ * by switching off, kept by idkptSetMaxBatch, idkptResetAccumulation and idkptBeginFrame.  The fold happens inside FinalDraw's loop over the samples of a batch, in submission
+ * order, into the slot the sample belongs to.  For each sample k:
+ *     nr = the value FinalDraw folds into Result for that sample (the traced radiance; the known sky colour of a tile pre-classified as sky; the regenerated textured-sky
+ *          sample; the DoDebugBVHTraversal colormap), w = the weight FinalDraw uses for it, 1 / ((float)accumulated + 1);
+ *     L  = (0.2126f * nr.x + 0.7152f * nr.y) + 0.0722f * nr.z;
+ *     m1 = m1 * (1 - w) + L * w;                 (GLSL mix, as Result's own fold)
+ *     m2 = m2 * (1 - w) + (L * L) * w.
+ * So m1 is the mean luminance of the n accumulated samples and m2 the mean of its square, as the running mean rounds them.
+ *
+ * The estimate.  idkptEstimateNoise(ctx, slot, p): slot -1 is the current slot; n = the slot's accumulated sample count; queued samples are launched first, the call runs in
+ * stream order and waits for nothing.  It reads the moments and changes nothing else — not the accumulated images, not the accumulation.  Per pixel:
+ *     var = fmaxf(m2 - m1 * m1, 0.0f);
+ *     e   = sqrtf(var / (float)(n - 1)) / (fmaxf(m1, 0.0f) + Epsilon);
+ *     a pixel whose m1 or m2 is not finite gets e = +Inf;
+ * the relative standard error of the pixel's mean luminance (e >= 0, never NaN).  Per tile of 8 x 8 pixels — tile (tx, ty) covers x in [8 tx, 8 tx + 8), y likewise, tiles in
+ * row-major order, tilesX = (width + 7) / 8, tilesY = (height + 7) / 8 — the call writes two floats, `mean` then `max`:
+ *     max   the maximum of e over the tile's pixels inside the image;
+ *     mean  with the 64 positions indexed by j = (y & 7) * 8 + (x & 7), positions outside the image counting as 0: the pairwise tree v[j] = v[j] + v[j ^ 1] for all j at once,
+ *           then the same with j ^ 2, j ^ 4, j ^ 8, j ^ 16, j ^ 32 (each level reads the values of the previous one); v[0] divided by the (float) count of pixels inside.
+ * The summary record is reset at the start of the call: TilesAbove = the number of tiles with mean > Threshold, MaxTileMean = the largest mean (an atomic max on the bit
+ * pattern: means are non-negative), Tiles = tilesX * tilesY, Samples = n.  Both aggregates are independent of the order the tiles are processed in.
+ * Errors of idkptEstimateNoise: a slot outside the ring, an Epsilon that is not finite and > 0, a Threshold that is not finite and >= 0, a NULL pointer:
+ * IDKPT_ERR_INVALID_ARGUMENT, before anything is launched.  The switch off, no size set, or n < 2: IDKPT_ERR_INVALID_OPERATION.
+ * Epsilon and Threshold defaults (1e-2, 0.05) are starting values nobody has tuned (profiles/noise.md).
+ *
+ * Readback.  idkptDownloadNoise synchronises like the other Download calls; bytes = tilesX * tilesY * 8; either pointer may be NULL (bytes is then not looked at).
+ * idkptGetNoiseDevicePtr is stream-ordered (idkptGetStream) and does not wait; 64 guard bytes of 0xA5 follow the tile map and the summary record.  Both refuse a slot that
+ * holds no estimate since the last resize (or since the switch was last turned on): IDKPT_ERR_INVALID_OPERATION.  idkptDownloadMoments (bytes = height * width * 16) and
+ * idkptGetMomentsDevicePtr read the slot's moments image, for tests and for a host's own statistics; they need the switch on and a size (IDKPT_ERR_INVALID_OPERATION without).
+ * enum idkpt_image does not grow.  The buffers of an estimate belong to a ring slot and follow the rules of the moments image. */
+typedef struct idkpt_noise {
+    float Epsilon;             /* > 0, finite: keeps the relative error of a black pixel finite.  default 1e-2 (not tuned) */
+    float Threshold;           /* >= 0, finite: a tile counts into TilesAbove when its mean error exceeds this.  default 0.05 (not tuned) */
+} idkpt_noise;
+typedef struct idkpt_noise_summary {
+    uint32_t TilesAbove;       /* tiles with mean > Threshold */
+    float    MaxTileMean;      /* the largest tile mean (+Inf when a tile holds a pixel with a non-finite moment) */
+    uint32_t Tiles;            /* tilesX * tilesY */
+    uint32_t Samples;          /* n of the call */
+} idkpt_noise_summary;
+IDKPT_API int32_t idkptSetNoiseEstimate(idkpt_ctx* ctx, int32_t enable);
+IDKPT_API int32_t idkptGetNoiseEstimate(idkpt_ctx* ctx, int32_t* outEnable);
+IDKPT_API int32_t idkptEstimateNoise(idkpt_ctx* ctx, int32_t slot, const idkpt_noise* noise);
+IDKPT_API int32_t idkptDownloadNoise(idkpt_ctx* ctx, int32_t slot, float* tiles, size_t bytes, idkpt_noise_summary* outSummary);
+IDKPT_API int32_t idkptGetNoiseDevicePtr(idkpt_ctx* ctx, int32_t slot, void** outTiles, void** outSummary, size_t* outTileBytes);
+IDKPT_API int32_t idkptDownloadMoments(idkpt_ctx* ctx, int32_t slot, float* rgba, size_t bytes);
+IDKPT_API int32_t idkptGetMomentsDevicePtr(idkpt_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes);   /* stream-ordered; the guard bytes follow *outBytes */
 
 /* ---- render ----------------------------------------------------------------------------- */
 /* PathTracer.ResetAccumulation (PathTracer.cs:334-337) */
