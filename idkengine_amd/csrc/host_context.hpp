@@ -70,6 +70,8 @@ struct DevOptions {
     int traceWaves = 0;          // one-wave workgroups per CU in the persistent grid (0: what LDS allows, at most 32)
     int gridHint = 2;            // bounce launches: grid = gridHint x the queue length the same bounce had in the previous batch (0: full grid)
     int deferLast = 1;           // the last bounce's continuation (state, queue) on demand instead of every frame, where only radiance of it is visible (kernels_shade.hpp k_shade_last)
+    int lastOcclusion = 1;       // ... and where only hit-or-miss of that bounce's traversal is read (no emission, no light hits: k_shade_last<false>), the launch stops every ray at its first
+                                 // accepted triangle (k_trace2 OCCL); the closest hits are traced when the continuation is asked for (finish_deferred).  0: the closest-hit launch every frame
     int graphProbe = 0;          // developer build only: capture the next batch into a hipGraph and time this many replays (tools/graph_probe.py)
     int gridMidWaves = 20;       // launches below GRID_MID_RAYS rays: one-wave workgroups per CU (0: off) — see small_launch_grid
     int gridRaysX4 = 6;          // small launches: quarter-rays per lane the persistent grid is sized for (from the previous batch's counts; 0: gridHint's rule alone)
@@ -222,7 +224,10 @@ struct dev_ctx {
     uint32_t* hCounts = nullptr; uint32_t* dCountsMirror = nullptr;   // host-mapped mirror of the queue lengths (written by k_scan_blocks, read by the host after a sync)
     bool sceneNested = false;       // every child box of every BLAS lies inside its parent's box (what k_trace2s's exactness argument needs; refits keep it)
     bool sceneNoEmission = false;   // no material / mesh of the uploaded scene emits and every texel is finite: a hit of the last bounce cannot change the radiance (k_shade_last)
-    struct { bool valid = false, allHits = false; int j = 0, side = 0, B = 0; uint32_t total = 0, Npad = 0; } defer;   // the last bounce of the last batch still owes its continuation (finish_deferred)
+    struct { bool valid = false, allHits = false; int j = 0, side = 0, B = 0; uint32_t total = 0, Npad = 0;
+             bool occl = false, pm = false; size_t ldsBytes = 0; uint32_t grid = 0; } defer;   // the last bounce of the last batch still owes its continuation (finish_deferred); occl: and its closest hits — the
+                                                                                             // launch was hit-or-miss (k_trace2 OCCL): pm = over the pixel-major list (hits per ray id), ldsBytes / grid = the plan's
+    uint64_t occlLaunches = 0;   // traversal launches that were hit-or-miss (idkpt_stats.LastOcclusionLaunches), since idkptResetStats
     DevBuf radSave, deferCount;
     bool countersDirty = true;   // the batch counters were not reset by the last k_final_draw (first batch, or a batch that failed half way)
     uint32_t* hOverflow = nullptr; uint32_t* dOverflow = nullptr;   // host-mapped word the kernels set when a traversal-stack push is dropped (checked after every sync)

@@ -58,6 +58,16 @@ static bool want_fused(const dev_ctx* ctx, uint32_t prev, bool known, int sample
     if (ctx->opt.fused >= 2) return true;
     return known && prev > 0u && prev < FUSED_MAX_RAYS && few_traversed(ctx, prev, std::max(1, samples));
 }
+// The deferred last bounce traced hit-or-miss (k_trace2 OCCL, kernels_trace.hpp; the argument: DESIGN.md §4) — THE rule, whole: launch_trace2 obeys what this says.
+// readsOnlyHitOrMiss: the bounce is deferred and a hit of it cannot add radiance (no emission, no light hits), so k_shade_last<false> reads `T == PT_FLOAT_MAX` of its hit records and
+// nothing else (rays whose throughput is not finite aside: write_trace_ready marks them, and the walk keeps a marked lane closest-hit).  Only the plain one-BLAS walk has the flavour:
+// Plain or Fast, not the fused launch, not a split one (split: what want_split said of this launch), one scene version, the stock kernels; the counting build keeps the closest-hit
+// walk, so its visit counts stay the reference's.  (Frames never run in query mode: idkptTraceRays has its own launch, host_queries.hpp.)
+static bool want_occlusion(const dev_ctx* ctx, const TracePlan& plan, bool readsOnlyHitOrMiss, bool split)
+{
+    return readsOnlyHitOrMiss && ctx->opt.lastOcclusion != 0 && !plan.fused && (plan.walk == Walk::Plain || plan.walk == Walk::Fast) && !(split && plan.splitOk)
+           && !plan.multiVer && !plan.counting && !ctx->counters && (ctx->opt.traceVariant == 0 || ctx->opt.traceVariant == 100);
+}
 static uint32_t small_launch_grid(uint32_t fullGrid, uint32_t prev, int hintMul, int raysX4, uint32_t midGrid)
 {
     if (prev == 0u || hintMul <= 0) return fullGrid;
@@ -119,6 +129,20 @@ static int finish_deferred(dev_ctx* ctx)
     Batch b; batch_views(ctx, b, ctx->defer.B, ctx->defer.Npad);
     b.side = ctx->defer.side; b.f = ctx->lastFrame; b.s = make_dscene_last(ctx); b.multiVer = ctx->lastMulti;           // the scene states the deferred batch was traced with (its slots are pinned until now: ver_writable)
     const uint32_t* q = ctx->queue[b.side].as<uint32_t>(); const uint32_t* cnt = ctx->deferCount.as<uint32_t>();               // (counts[j] itself was reset by the batch's last kernel)
+    if (ctx->defer.occl) {
+        // the bounce was traced hit-or-miss (k_trace2 OCCL): its closest hits first — the plain closest-hit kernel over the same list, the same records (trRec and the pixel-major list belong
+        // to batches alone, and the next batch drops this continuation before it touches them), the same hit indexing.  Nothing of it is counted: RaysTraced counted the bounce at its scan,
+        // TraceLaunches / TraceMsTotal come from events recorded around a batch's launches.  The launch's work-list words are zero (k_final_draw reset them) unless something left them dirty.
+        const int j = ctx->defer.j;
+        if (ctx->countersDirty) HIPC(hipMemsetAsync(b.work, 0, WORK_WORDS * 4, b.st));
+        // The plan is Plain on purpose, whatever the batch walked: Plain reads s.nodes only — pinned for the deferred batch — and so does not depend on DScene::pairNodes still being
+        // derived, and its hits are FAST's bit for bit (kernels_trace.hpp).  Every other field of the plan is off: no packets, nothing fused, one version, no counting, no split.
+        TracePlan p{}; p.walk = Walk::Plain; p.ldsBytes = ctx->defer.ldsBytes; p.grid = ctx->defer.grid;
+        Frame ft = b.f; if (ctx->defer.pm) ft.hitsByRid = 0;                  // (the PRIMARY instantiations read a list of ray ids and store per ray id: trace_bounce)
+        if (ctx->defer.pm) launch_trace2<true>(ctx, p, p.grid, b.st, b.s, ft, b.rays, b.tr, b.hits, ctx->pmList.as<uint32_t>(), cnt, b.work + j, b.counters, false, j);
+        else launch_trace2<false>(ctx, p, p.grid, b.st, b.s, ft, b.rays, b.tr, b.hits, q, cnt, b.work + j, b.counters, false, j);
+        ctx->defer.occl = false;
+    }
     with_flag(ctx->defer.allHits, [&](auto ALL) { launch(k_restore_last<ALL>, dim3(b.gridTotal), dim3(256), 0, b.st, b.rays, b.hits, q, cnt, ctx->radSave.as<float4>(), b.f.hitsByRid); });
     { int rc = bounce_tail(b, ctx->defer.j, q, cnt, nullptr, nullptr, false, b.tr); if (rc) return rc; }
     HIPC(hipGetLastError());
@@ -347,23 +371,28 @@ static int sort_queue(Batch& b, uint32_t* q, uint32_t* k, const uint32_t* cnt)
 
 // The traversal launch of bounce j.  Its grid: the queue length is only known on the device; the length the same bounce had in the previous batch (pinned copy,
 // possibly one batch stale) is a good predictor, and a grid that is too small or too large only costs time (the waves are persistent)
-static void trace_bounce(Batch& b, int j, const uint32_t* q, const uint32_t* cnt)
+// readsOnlyHitOrMiss: nothing but hit-or-miss of this launch's records is read (flush_batch); returns whether the launch was the hit-or-miss one (want_occlusion)
+static bool trace_bounce(Batch& b, int j, const uint32_t* q, const uint32_t* cnt, bool readsOnlyHitOrMiss)
 {
     dev_ctx* ctx = b.ctx; hipStream_t st = b.st; const int B = b.B;
     TRACE_T0();
     const bool known = ctx->lastFast && ctx->lastBatch == B && ctx->hBases != nullptr; const uint32_t prev = ctx->hBases ? ctx->hBases[(size_t)j * BS + B] : 0u;
     uint32_t gridj = b.traceGrid;
+    const bool split = want_split(ctx, prev, known, B), occl = b.fast && want_occlusion(ctx, b.plan, readsOnlyHitOrMiss, split);
+    if (occl) ctx->occlLaunches++;
     if (ctx->opt.gridHint > 0 && ctx->lastBatch == B && ctx->hBases) gridj = small_launch_grid(b.traceGrid, ctx->hBases[(size_t)j * BS + B], ctx->opt.gridHint, ctx->opt.gridRaysX4, b.midGrid);
     if (b.fast && b.pmBounce && j == 1) {   // the list k_shade_first wrote: ray ids, hits stored per ray id (the PRIMARY instantiations read exactly that)
         Frame ft = b.f; ft.hitsByRid = 0;
-        launch_trace2<true>(ctx, b.plan, gridj, st, b.s, ft, b.rays, b.tr, b.hits, b.pmList, b.pmCount, b.work + j, b.counters, want_split(ctx, prev, known, B), j);
-    } else if (b.fast) launch_trace2<false>(ctx, b.plan, gridj, st, b.s, b.f, b.rays, b.tr, b.hits, q, cnt, b.work + j, b.counters, want_split(ctx, prev, known, B), j);
+        launch_trace2<true>(ctx, b.plan, gridj, st, b.s, ft, b.rays, b.tr, b.hits, b.pmList, b.pmCount, b.work + j, b.counters, split, j, occl);
+    } else if (b.fast) launch_trace2<false>(ctx, b.plan, gridj, st, b.s, b.f, b.rays, b.tr, b.hits, q, cnt, b.work + j, b.counters, split, j, occl);
     else with_flag(ctx->counters, [&](auto COUNT) { launch(k_trace_queue<COUNT>, dim3(b.traceGrid), dim3(WAVE), b.plan.ldsBytes, st, b.s, b.f, b.rays, b.hits, q, cnt, b.work + j, b.counters); });
     TRACE_T1();
+    return occl;
 }
 
 // The last bounce where only its radiance is visible in the frame (kernels_shade.hpp k_shade_last): state, queue and counts follow on demand (finish_deferred)
-static int defer_last_bounce(Batch& b, int j, const uint32_t* q, const uint32_t* cnt, bool allHits)
+// occl: its traversal launch was the hit-or-miss one — finish_deferred traces the closest hits first
+static int defer_last_bounce(Batch& b, int j, const uint32_t* q, const uint32_t* cnt, bool allHits, bool occl)
 {
     dev_ctx* ctx = b.ctx;
     HIPC(ctx->radSave.ensure((size_t)ctx->maxBatch * ctx->Npad * 16)); HIPC(ctx->deferCount.ensure(64));
@@ -371,6 +400,7 @@ static int defer_last_bounce(Batch& b, int j, const uint32_t* q, const uint32_t*
     if (allHits) with_flag(b.multiVer, [&](auto VER) { shade_last(std::true_type{}, VER); });
     else shade_last(std::false_type{}, std::false_type{});            // (misses only: the sky is not versioned)
     ctx->defer.allHits = allHits; ctx->defer.valid = true; ctx->defer.j = j; ctx->defer.side = b.side; ctx->defer.B = b.B; ctx->defer.total = b.total; ctx->defer.Npad = b.Npad;
+    ctx->defer.occl = occl; ctx->defer.pm = b.pmBounce && j == 1; ctx->defer.ldsBytes = b.plan.ldsBytes; ctx->defer.grid = b.traceGrid;
     return IDKPT_OK;
 }
 
@@ -416,8 +446,11 @@ static int flush_batch(dev_ctx* ctx)
         b.f.hitsByRid = (b.plan.fused || (b.pmBounce && j == 1)) ? 1 : 0;     // how this bounce's hit records are indexed (what its shading kernels are told)
         if ((rc = exchange_bases(b, j, q, gbase))) return rc;
         if (ctx->st.DoRaySorting && j > 1) if ((rc = sort_queue(b, q, k, cnt))) return rc;
-        if (!b.plan.fused) trace_bounce(b, j, q, cnt);
-        if (deferLast && j == b.depth - 1 && gbase == nullptr) { if ((rc = defer_last_bounce(b, j, q, cnt, deferAllHits))) return rc; break; }
+        // (the deferred last bounce of a scene without emission or light hits — only hit-or-miss of its records is read — may be traced hit-or-miss: want_occlusion holds the whole rule)
+        const bool deferThis = deferLast && j == b.depth - 1 && gbase == nullptr;
+        bool tookOccl = false;
+        if (!b.plan.fused) tookOccl = trace_bounce(b, j, q, cnt, deferThis && !deferAllHits);
+        if (deferThis) { if ((rc = defer_last_bounce(b, j, q, cnt, deferAllHits, tookOccl))) return rc; break; }
         if ((rc = bounce_tail(b, j, q, cnt, gbase, (unsigned long long*)(j + 1 < b.depth ? b.counters + 2 : nullptr), ctx->evBounce != nullptr, b.fast ? b.tr : b.trNone))) return rc;
         b.side = 1 - b.side;
     }

@@ -23,7 +23,10 @@ DEV void write_trace_ready(const DScene& s, const Frame& f, const TraceBufs& tr,
     const float4* root = s.nodes + 2 * (size_t)s.descs[inst.BlasId].NodeOffset + 2;
     float t1;
     const float rootT = RayBoxIntersect(lo, iv, root[0], root[1], &t1) ? t1 : __builtin_inff();
-    tr.rec[4 * (size_t)rid] = make_float4(lo.x, lo.y, lo.z, rootT); tr.rec[4 * (size_t)rid + 1] = make_float4(ld.x, ld.y, ld.z, 0.0f);
+    // ld.w = 1 marks a ray whose throughput is not finite: should the launch that traces it be the hit-or-miss one (k_trace2 OCCL: the deferred last bounce), this ray still gets its
+    // closest hit — k_shade_last runs ShadeHit on it (0 * inf is not 0).  The throughput stored with the ray state is this one; no other kernel looks at the word outside query mode.
+    const float wantClosest = (__builtin_isfinite(r.throughput.x) && __builtin_isfinite(r.throughput.y) && __builtin_isfinite(r.throughput.z)) ? 0.0f : 1.0f;
+    tr.rec[4 * (size_t)rid] = make_float4(lo.x, lo.y, lo.z, rootT); tr.rec[4 * (size_t)rid + 1] = make_float4(ld.x, ld.y, ld.z, wantClosest);
     tr.rec[4 * (size_t)rid + 2] = make_float4(iv.x, iv.y, iv.z, 0.0f);
 }
 

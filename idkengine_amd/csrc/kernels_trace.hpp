@@ -310,11 +310,16 @@ __global__ __launch_bounds__(1024) void k_gen_primary(DScene s0, Frame f, RayBuf
 // that BOTH boxes' slabs are six 2-wide subtractions and six 2-wide multiplications (the reference's layout allows eight + eight scalar ones); leaf flags derived once; no stack-full
 // test (the stack is sized from the tree's validated need: k_trace2's own comment calls the test unreachable) and no stack-empty test (the row a pop of the empty stack reads holds 0,
 // and the lane is finished then): 62 -> 53 vector instructions per step, every number the same operation on the same operands — bit-identical (tests/test_gpu_parity.py & co.).
-template <bool PRIMARY, bool COUNT, int REFILL_MIN = 32, int OCC = 1, bool PROF = false, int LEAF_MIN = 24, int MODE = 0, int DBG = 0, bool VER = false, bool ANY = false, bool FAST = false>
+// OCCL (MODE 0, one scene version, no counters; with or without FAST, either leaf phase): hit or miss only — the deferred last bounce of a scene without emission or light hits, whose
+// only reader (k_shade_last<false>) asks `T == PT_FLOAT_MAX` and nothing else.  The node step is the closest-hit one (nearer child first); the first triangle accepted by `t < T` ends the
+// lane: its stack, its parked leaf's remaining triangles are dropped.  Hit-or-miss is what the closest-hit walk reports, ray for ray; T of a hit is SOME accepted triangle's,
+// triangle id and barycentrics with it.  A ray whose producer marked it (record[1].w != 0: its throughput is not finite, k_shade_last runs ShadeHit on its real hit) walks closest-hit.
+template <bool PRIMARY, bool COUNT, int REFILL_MIN = 32, int OCC = 1, bool PROF = false, int LEAF_MIN = 24, int MODE = 0, int DBG = 0, bool VER = false, bool ANY = false, bool FAST = false, bool OCCL = false>
 __global__ __launch_bounds__(WAVE, OCC) void k_trace2(DScene s, Frame f, RayBufs rays, TraceBufs tr, HitBufs hits, const uint32_t* list, const uint32_t* countPtr, uint32_t* workCounter, uint64_t* counters)
 {
     static_assert(MODE >= 0 && MODE <= 2 && (DBG == 0 || DBG == 16), "k_trace2: MODE 0-2, DBG 0 or 16 (pooled leaf phase)");
     static_assert(!FAST || (MODE == 0 && !COUNT && !VER && !ANY && !PROF), "k_trace2: FAST is the plain one-BLAS closest-hit walk");
+    static_assert(!OCCL || (MODE == 0 && !COUNT && !VER && !ANY && !PROF), "k_trace2: OCCL is the plain one-BLAS walk that stops at the first accepted triangle");
     constexpr bool MULTI = MODE != 0, TLAS = MODE == 2;
     // DBG 16 ("pooled leaves", MODE 0): the leaf phase tests the wave's (ray, triangle) PAIRS with all 64 lanes in one round trip instead of every parked lane
     // walking its own 1-8 triangles one dependent fetch after the other with 18-22 lanes active (instrumented: 23-48 pairs per leaf phase in 2.0-3.1 loop trips).
@@ -365,6 +370,7 @@ __global__ __launch_bounds__(WAVE, OCC) void k_trace2(DScene s, Frame f, RayBufs
     float hitT = 0.0f, hbx = 0.0f, hby = 0.0f; uint32_t hitTri = ~0u, hitXform = 0;
     uint32_t nPairs = 0, nTris = 0;
     bool ovf = false;                      // a push found the stack full (reported once, when the wave ends)
+    bool occl = false;                     // OCCL: this lane's ray ends at its first accepted triangle (false: its producer asked for the closest hit)
     // PROF: per-wave cycle buckets [refill, node, leaf, other], step counts and active-lane sums (developer instrumentation)
     unsigned long long pc[4] = {0, 0, 0, 0}, pn[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     unsigned long long tPrev = PROF ? __builtin_amdgcn_s_memtime() : 0ull;
@@ -427,7 +433,7 @@ __global__ __launch_bounds__(WAVE, OCC) void k_trace2(DScene s, Frame f, RayBufs
                 else {
                     // local-space ray and 1/dir were prepared by the (coherent, full-lane) kernel that produced this ray
                     float rootT;
-                    { float4 a = tr.rec[4 * (size_t)idx], b = tr.rec[4 * (size_t)idx + 1], c = tr.rec[4 * (size_t)idx + 2]; ro = mk3(a.x, a.y, a.z); rd = mk3(b.x, b.y, b.z); invDir = mk3(c.x, c.y, c.z); rootT = a.w; }
+                    { float4 a = tr.rec[4 * (size_t)idx], b = tr.rec[4 * (size_t)idx + 1], c = tr.rec[4 * (size_t)idx + 2]; ro = mk3(a.x, a.y, a.z); rd = mk3(b.x, b.y, b.z); invDir = mk3(c.x, c.y, c.z); rootT = a.w; if (OCCL) occl = b.w == 0.0f; }
                     const bool enter = rootT < hitT;   // root test (:32-39): the box arithmetic ran in the kernel that produced the ray (record[0].w = tMin, +inf = miss)
                     active = true; leafPending = false; sp = stkBase; top = enter ? 2u : 0u;
                 }
@@ -607,7 +613,10 @@ __global__ __launch_bounds__(WAVE, OCC) void k_trace2(DScene s, Frame f, RayBufs
                         const int from = (int)((j & 63u) << 2);
                         const float t = __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(pt)));
                         const float by = __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(pby))), bz = __int_as_float(__builtin_amdgcn_ds_bpermute(from, __float_as_int(pbz)));
-                        if (k < cnt && j < 64u && t < hitT) { hitTri = leafFirst + k + (MULTI ? triOff : triOffset); hbx = 1.0f - by - bz; hby = by; hitT = t; hitXform = MULTI ? xformId : inst.MeshTransformId; }
+                        if (k < cnt && j < 64u && t < hitT) {
+                            hitTri = leafFirst + k + (MULTI ? triOff : triOffset); hbx = 1.0f - by - bz; hby = by; hitT = t; hitXform = MULTI ? xformId : inst.MeshTransformId;
+                            if (OCCL && occl) top = 0u;      // (whatever else of this leaf is accepted only lowers T: still a hit; the lane retires below)
+                        }
                     }
                     __builtin_amdgcn_wave_barrier();
                     if (base + 64u >= total) leafPending = false;
@@ -624,6 +633,7 @@ __global__ __launch_bounds__(WAVE, OCC) void k_trace2(DScene s, Frame f, RayBufs
                 float by, bz, t;
                 if (RayTriangleIntersect(ro, rd, mk3(a.x, a.y, a.z), mk3(b.x, b.y, b.z), mk3(c.x, c.y, c.z), &by, &bz, &t) && t < hitT) {
                     hitTri = i; hbx = 1.0f - by - bz; hby = by; hitT = t; hitXform = MULTI ? xformId : inst.MeshTransformId;
+                    if (OCCL && occl) { top = 0u; break; }   // hit or miss is all that is read: nothing of this ray is left to do (sp is reset with the lane's next ray)
                     if (ANY) {   // the first intersection found wins: nothing of this ray is left to do
                         top = 0u; sp = stkBase;
                         if (MULTI) { instIdx = (uint32_t)s.instanceCount; moreInst = false; }

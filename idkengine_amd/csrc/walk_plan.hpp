@@ -21,6 +21,7 @@ namespace walk {
 // On top of the batch's walk, per launch:
 //   any-hit queries  k_trace2<true, false, 32, 1, false, 24, M, 0, false, true>, M = 0 / 1 / 2 by scene shape (Plain / Loop / Tlas)
 //   packetPrimary    k_trace_packet<true[, true]> + k_packet_mirror + flagged: the primary launch of bounce 0 on one BLAS or on the unified tree (option packet: 1 = by measurement, the default)
+//   occlusion        k_trace2<P, false, 32, 1, false, 24, 0, 0 | 16, false, false, false | true, true> instead of Plain / Fast: the deferred last bounce where only hit-or-miss of it is read (option last_occlusion, host_schedule.hpp flush_batch)
 //   split            k_trace2s<P> instead of Plain / Fast: small launches of sparse views (want_split);   fused: k_trace_fused<32> instead of both launches of a RayDepth-2 batch (default off)
 //   flagged          one BLAS: k_trace2<P, false>; several instances: k_trace_inst<P, true> while a lane's mask fits its LDS rows, else k_trace2<P, false, 16, 1, false, 24, 1, 0, false>
 enum class Walk { Generic, Plain, Fast, Loop, Tlas, Wide, OwnTlas, Unified, General, Sieve };

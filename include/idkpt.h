@@ -231,8 +231,13 @@ typedef struct idkpt_stats {
     uint64_t InstUnifiedLaunches;  /* traversal launches that walked it, since idkptResetStats (their flagged rays count in InstTlasFlaggedRays) */
     uint32_t InstUnifiedEntries;   /* subtrees of the BLASes under its top, as last derived (0: not in use) */
     uint32_t InstUnifiedTopDepth;  /* depth of that top */
+    /* the deferred last bounce traced hit-or-miss (developer option "last_occlusion", csrc/kernels_trace.hpp k_trace2 OCCL).  Added at ABI 12 without a new number: see below */
+    uint64_t LastOcclusionLaunches; /* traversal launches that stopped every ray at its first accepted triangle, since idkptResetStats (the closest-hit launch that idkptDownloadRays & co. ask for
+                                     * afterwards is neither counted here nor in TraceLaunches / RaysTraced) */
 } idkpt_stats;
-/* The layout above only ever GROWS at its end, and IDKPT_ABI_VERSION counts the growths (and every other change a host compiled against an older header could trip over: new
+/* The layout above only ever GROWS at its end.  IDKPT_ABI_VERSION counted its growths up to ABI 3; since idkptGetStatsSized exists a growth of this struct no longer takes a number
+ * (LastOcclusionLaunches came at 12 without one): the size a host passes IS its version of the struct, and a host that was not built from this tree must use idkptGetStatsSized —
+ * idkptGetStats writes sizeof(idkpt_stats) of the LIBRARY's header, which is more than an older host's struct holds.  The number counts the rest (every change a host compiled against an older header could trip over: new
  * enum values of idkpt_buffer or idkpt_texture_format, new fields of idkpt_texture, new entry points: 5 = idkptComputeSky / idkptUpdateSky / idkptDownloadSky, 6 = idkptPresent / idkptDownloadDisplay / idkptGetDisplayDevicePtr,
  * 7 = idkptBloom / idkptGetBloomInfo / idkptDownloadBloom / idkptGetBloomDevicePtr, 8 = idkptUnprojectSky,
  * 9 = idkptSetPresentationSize / idkptGetPresentationSize / idkptGetBloomRoute / idkptGetBloomChainDevicePtr, 10 = idkptDownloadTileClasses, 11 = idkptCollideSpheres / idkptCollideSpheresDevice,
@@ -829,6 +834,10 @@ IDKPT_API int32_t idkptEnableTiming(idkpt_ctx* ctx, int32_t enable);
  *     "inst_sieve_overlap" 0-100 (50*) ... only up to this overlap (as above)
  *     "query_scheduler"  0 / 1*      idkptTraceRays through k_trace2's scheduler (0: thread-per-ray kernel, the cross-check)
  *     "defer_last"       0 / 1*      without AOVs only the radiance of a sample's last bounce is computed per frame; its continuation when a host asks (idkptDownloadRays ...)
+ *     "last_occlusion"   0 / 1*      ... and where a hit of that bounce cannot add radiance (no emission in the scene, no light hits) its traversal launch only answers hit-or-miss: every ray stops at the
+ *                                    first triangle it meets (k_trace2 OCCL, csrc/kernels_trace.hpp; rays whose throughput is not finite keep their closest hit).  One BLAS instance, one scene version in the
+ *                                    batch, counters off, a launch that is not split, no multi-GPU bounce exchange; otherwise, and with 0, the closest-hit launch.  The closest hits are traced when the
+ *                                    continuation is asked for.  Frames, ray state, queues and counts are bit-identical either way; idkpt_stats.LastOcclusionLaunches counts the launches
  *     "gen_pixel_major"  >= 0 (8*)   batches of at least this many samples hand their primary rays to the traversal pixel by pixel (a wave = 4 pixels x 16 samples instead of an 8x8 tile of one
  *                                    sample; profiles/r05_pixel_major.md); 0 = never.   "gen_group_max" 1-16 (16*): samples per group of that list
  *     "bounce_pixel_major" 0-2 (1*) the first bounce traced in that order too (its own work list, hits per ray id): 0 never, 1 on sparse views, 2 always
