@@ -1,13 +1,11 @@
 // host_bloom.hpp — idkptBloom / idkptGetBloomInfo / idkptDownloadBloom / idkptGetBloomDevicePtr: Bloom.Compute (Source/Render/Bloom.cs:56-127) on the device
 // (kernels: kernels_bloom.hpp).  Part of the single translation unit idkpt.hip (included there, in this order).
-// Behaves as idkptPresent does (host_readback.hpp): queued samples are launched first, nothing waits for the GPU, buffers belong to a ring slot and a frame size —
-// three per slot (the down chain, the up chain: RGBA16F levels one behind the other; the expanded RGBA32F image), allocated at the slot's first bloom, released by
-// alloc_frame_impl, kept by idkptSetMaxBatch, each followed by BLOOM_GUARD_BYTES of 0xA5 that nothing writes.
-// The chain and the expanded image have the presentation size (host_readback.hpp pres_w / pres_h; the render size by default), the image they start from the render size.
+// Queued samples are launched first, nothing waits for the GPU.  A frame product (host_context.hpp, "frame products": the life cycle of the buffers) with three buffers per
+// slot: the down chain, the up chain (RGBA16F levels one behind the other), the expanded RGBA32F image.
+// The chain and the expanded image have the presentation size (host_context.hpp pres_w / pres_h; the render size by default), the image they start from the render size.
 // One device, the whole frame: bloom is a global filter (the last level mixes the whole image), a shard of the rows would need halos as wide as the chain.
 #pragma once
 
-#define BLOOM_GUARD_BYTES 64
 static size_t bloom_level_texels(int w0, int h0, int level) { return (size_t)bloomt::level_dim(w0, level) * (size_t)bloomt::level_dim(h0, level); }
 static size_t bloom_level_offset(int w0, int h0, int level) { size_t t = 0; for (int l = 0; l < level; l++) t += bloom_level_texels(w0, h0, l); return t; }   // texels in front of `level`
 // k_bloom_down0 stages SRC_TILE source texels per axis: true when every tile of a level of `dsize` texels reading `ssize` texels stays inside
@@ -19,14 +17,6 @@ static bool bloom_tile_spans_fit(int dsize, int ssize)
     }
     return true;
 }
-static int bloom_ensure(dev_ctx* ctx, DevBuf& buf, size_t& have, size_t bytes)
-{
-    if (buf.p && have == bytes) return IDKPT_OK;
-    HIPC(buf.ensure(bytes + BLOOM_GUARD_BYTES));
-    HIPC(hipMemsetAsync((char*)buf.p + bytes, 0xA5, BLOOM_GUARD_BYTES, ctx->stream));
-    have = bytes;
-    return IDKPT_OK;
-}
 
 static int32_t dev_Bloom(dev_ctx* ctx, int32_t slot, int32_t image, const idkpt_bloom* b)
 {
@@ -37,9 +27,9 @@ static int32_t dev_Bloom(dev_ctx* ctx, int32_t slot, int32_t image, const idkpt_
     REQUIRE(fin(b->Threshold) && fin(b->MaxColor), "idkptBloom: Threshold and MaxColor must be finite");
     REQUIRE(b->MinusLods >= 0, "idkptBloom: MinusLods must not be negative");
     if (ctx->W <= 0 || !ctx->frameOk) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptBloom: no frame buffers (idkptSetSize not called)");
-    if (present_scaled(ctx) && (ctx->grouped || !holds_whole_frame(ctx)))
+    if (present_scaled(ctx) && !owns_whole_frame(ctx))
         return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptBloom: a presentation size other than the render size (idkptSetPresentationSize) needs one device that holds the whole frame; this context holds a shard of the rows");
-    if (ctx->rowMod != 1 || ctx->rowRem != 0 || ctx->rows != ctx->H) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptBloom: the context holds a shard of the rows (idkptSetRowSharding / idkptSetRowBands / idkptSetRowRange); bloom needs the whole frame on one device");
+    if (!holds_whole_frame(ctx)) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptBloom: the context holds a shard of the rows (idkptSetRowSharding / idkptSetRowBands / idkptSetRowRange); bloom needs the whole frame on one device");
     // the chain is sized from the PRESENTATION size (Bloom.SetSize(presentRes), Application.cs:570-586), which is the render size unless idkptSetPresentationSize said otherwise
     const int W = ctx->W, H = ctx->H, pw = pres_w(ctx), ph = pres_h(ctx);
     if (pw < 2 || ph < 2) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptBloom: the frame must be at least 2 x 2 (level 0 is width / 2 x height / 2)");
@@ -52,13 +42,12 @@ static int32_t dev_Bloom(dev_ctx* ctx, int32_t slot, int32_t image, const idkpt_
     HIPC(hipSetDevice(ctx->device));
     FLUSH_KEEP();                                        // stream-ordered behind what was queued (as idkptPresent)
     { int rc = check_overflow(ctx); if (rc) return rc; }   // (no wait: see idkptGetFrameDevicePtr)
-    if (ctx->bloom.size() != (size_t)ctx->ringSize) { for (BloomSlot& s : ctx->bloom) s.release(); ctx->bloom.assign(ctx->ringSize, BloomSlot()); }
-    BloomSlot& s = ctx->bloom[slot];
+    BloomSlot& s = FrameProducts::slot(ctx->products.bloom, ctx->ringSize, slot);
     s.valid = false;
-    { int rc = bloom_ensure(ctx, s.down, s.downBytes, bloom_level_offset(w0, h0, levels) * 8); if (rc) return rc; }
-    { int rc = bloom_ensure(ctx, s.up, s.upBytes, bloom_level_offset(w0, h0, levels - 1) * 8); if (rc) return rc; }
-    { int rc = bloom_ensure(ctx, s.out, s.outBytes, (size_t)pw * ph * 16); if (rc) return rc; }
-    auto lvl = [&](DevBuf& buf, int l) { return (uint2*)buf.p + bloom_level_offset(w0, h0, l); };
+    HIPC(s.down.ensure(ctx->stream, bloom_level_offset(w0, h0, levels) * 8));
+    HIPC(s.up.ensure(ctx->stream, bloom_level_offset(w0, h0, levels - 1) * 8));
+    HIPC(s.out.ensure(ctx->stream, (size_t)pw * ph * 16));
+    auto lvl = [&](GuardedBuf& buf, int l) { return buf.as<uint2>() + bloom_level_offset(w0, h0, l); };
     auto dim = [](int d0, int l) { return bloomt::level_dim(d0, l); };
     auto grid = [](int w, int h) { return dim3((unsigned)((w + bloomk::TILE - 1) / bloomk::TILE), (unsigned)((h + bloomk::TILE - 1) / bloomk::TILE)); };
     // down pass 0: the image, Lod 0, Prefilter -> down level 0
@@ -72,25 +61,17 @@ static int32_t dev_Bloom(dev_ctx* ctx, int32_t slot, int32_t image, const idkpt_
         const uint2* a = l == levels - 2 ? lvl(s.down, l + 1) : lvl(s.up, l + 1);
         hipLaunchKernelGGL((k_bloom_pass<1>), grid(dim(w0, l), dim(h0, l)), dim3(256), 0, ctx->stream, a, (const uint2*)lvl(s.down, l + 1), dim(w0, l + 1), dim(h0, l + 1), lvl(s.up, l), dim(w0, l), dim(h0, l), 0, 0.0f, 0.0f);
     }
-    hipLaunchKernelGGL(k_bloom_expand, dim3((unsigned)(((size_t)pw * ph + 255) / 256)), dim3(256), 0, ctx->stream, (const uint2*)lvl(s.up, 0), w0, h0, (float4*)s.out.p, pw, ph);
+    hipLaunchKernelGGL(k_bloom_expand, dim3((unsigned)(((size_t)pw * ph + 255) / 256)), dim3(256), 0, ctx->stream, (const uint2*)lvl(s.up, 0), w0, h0, s.out.as<float4>(), pw, ph);
     HIPC(hipGetLastError());
     s.levels = levels; s.w0 = w0; s.h0 = h0; s.direct = direct; s.valid = true;
     return IDKPT_OK;
 }
-// the last bloom of a slot; INVALID_OPERATION when the slot was not bloomed since the last resize
-static int32_t bloom_of(dev_ctx* ctx, const char* who, int32_t slot, BloomSlot** out)
-{
-    REQUIRE(slot >= -1 && slot < ctx->ringSize, std::string(who) + ": slot outside the frame ring (-1: the current slot)");
-    if (slot < 0) slot = ctx->curSlot;
-    if ((size_t)slot >= ctx->bloom.size() || !ctx->bloom[slot].valid) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, std::string(who) + ": the slot was not bloomed since the last resize (idkptBloom)");
-    *out = &ctx->bloom[slot];
-    return IDKPT_OK;
-}
+#define BLOOM_NONE ": the slot was not bloomed since the last resize (idkptBloom)"
 static int32_t dev_GetBloomInfo(dev_ctx* ctx, int32_t slot, int32_t* levels, int32_t* w0, int32_t* h0)
 {
     if (!ctx) return IDKPT_ERR_INVALID_ARGUMENT;
     BloomSlot* s = nullptr;
-    { int rc = bloom_of(ctx, "idkptGetBloomInfo", slot, &s); if (rc) return rc; }
+    { int rc = slot_of(ctx, ctx->products.bloom, "idkptGetBloomInfo", slot, BLOOM_NONE, &s); if (rc) return rc; }
     if (levels) *levels = s->levels;
     if (w0) *w0 = s->w0;
     if (h0) *h0 = s->h0;
@@ -102,16 +83,17 @@ static int32_t dev_GetBloomChainDevicePtr(dev_ctx* ctx, int32_t slot, int32_t ch
     if (!ctx || !outPtr) return IDKPT_ERR_INVALID_ARGUMENT;
     REQUIRE(chain == 0 || chain == 1, "idkptGetBloomChainDevicePtr: chain must be 0 (down) or 1 (up)");
     BloomSlot* s = nullptr;
-    { int rc = bloom_of(ctx, "idkptGetBloomChainDevicePtr", slot, &s); if (rc) return rc; }
-    *outPtr = chain ? s->up.p : s->down.p;
-    if (outBytes) *outBytes = chain ? s->upBytes : s->downBytes;
+    { int rc = slot_of(ctx, ctx->products.bloom, "idkptGetBloomChainDevicePtr", slot, BLOOM_NONE, &s); if (rc) return rc; }
+    const GuardedBuf& b = chain ? s->up : s->down;
+    *outPtr = b.mem.p;
+    if (outBytes) *outBytes = b.bytes;
     return IDKPT_OK;
 }
 static int32_t dev_GetBloomRoute(dev_ctx* ctx, int32_t slot, int32_t* route)
 {
     if (!ctx || !route) return IDKPT_ERR_INVALID_ARGUMENT;
     BloomSlot* s = nullptr;
-    { int rc = bloom_of(ctx, "idkptGetBloomRoute", slot, &s); if (rc) return rc; }
+    { int rc = slot_of(ctx, ctx->products.bloom, "idkptGetBloomRoute", slot, BLOOM_NONE, &s); if (rc) return rc; }
     *route = s->direct ? IDKPT_BLOOM_ROUTE_DIRECT : IDKPT_BLOOM_ROUTE_TILED;
     return IDKPT_OK;
 }
@@ -120,22 +102,18 @@ static int32_t dev_DownloadBloom(dev_ctx* ctx, int32_t slot, int32_t chain, int3
     if (!ctx || !dst) return IDKPT_ERR_INVALID_ARGUMENT;
     REQUIRE(chain == 0 || chain == 1, "idkptDownloadBloom: chain must be 0 (down) or 1 (up)");
     BloomSlot* s = nullptr;
-    { int rc = bloom_of(ctx, "idkptDownloadBloom", slot, &s); if (rc) return rc; }
+    { int rc = slot_of(ctx, ctx->products.bloom, "idkptDownloadBloom", slot, BLOOM_NONE, &s); if (rc) return rc; }
     REQUIRE(level >= 0 && level < s->levels - chain, "idkptDownloadBloom: level outside the chain (the down chain has `levels` levels, the up chain one fewer)");
     const size_t need = bloom_level_texels(s->w0, s->h0, level) * 8;
     REQUIRE(bytes == need, "idkptDownloadBloom: bytes must equal the level's width*height*8");
-    HIPC(hipSetDevice(ctx->device));
-    FLUSH_KEEP();
-    HIPC(hipMemcpyAsync(dst, (const char*)(chain ? s->up.p : s->down.p) + bloom_level_offset(s->w0, s->h0, level) * 8, need, hipMemcpyDeviceToHost, ctx->stream));
-    SYNC_CHECKED();
-    return IDKPT_OK;
+    return download_behind_queue(ctx, dst, (chain ? s->up : s->down).as<const char>() + bloom_level_offset(s->w0, s->h0, level) * 8, need);
 }
 static int32_t dev_GetBloomDevicePtr(dev_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes)
 {
     if (!ctx || !outPtr) return IDKPT_ERR_INVALID_ARGUMENT;
     BloomSlot* s = nullptr;
-    { int rc = bloom_of(ctx, "idkptGetBloomDevicePtr", slot, &s); if (rc) return rc; }
-    *outPtr = s->out.p;
-    if (outBytes) *outBytes = s->outBytes;
+    { int rc = slot_of(ctx, ctx->products.bloom, "idkptGetBloomDevicePtr", slot, BLOOM_NONE, &s); if (rc) return rc; }
+    *outPtr = s->out.mem.p;
+    if (outBytes) *outBytes = s->out.bytes;
     return IDKPT_OK;
 }

@@ -34,28 +34,94 @@ struct PinnedStage {
     void release() { if (host) (void)hipHostFree(host); for (hipEvent_t& e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; } host = nullptr; }
 };
 
-// idkptBloom (host_bloom.hpp): the buffers of one ring slot — RGBA16F levels of the down and the up chain, the expanded RGBA32F image — and what the last bloom made of them
+// Single-buffered pinned staging of one large host array a call uploads (idkptUpdateSky's faces, idkptUploadDenoised's image): the array is borrowed for the call only
+// and the copy must not make the call wait for the stream.  One buffer that grows to the largest upload so far; stage() waits only for the copy that last read it (normally
+// long finished) and fills it, the caller enqueues its copies from `host` and then records them with done().
+struct PinnedUpload {
+    char* host = nullptr; size_t bytes = 0; hipEvent_t ev = nullptr;
+    hipError_t stage(const void* src, size_t n)
+    {
+        hipError_t e;
+        if (!ev) { if ((e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) != hipSuccess) return e; }
+        else if ((e = hipEventSynchronize(ev)) != hipSuccess) return e;
+        if (bytes < n) {
+            if (host) (void)hipHostFree(host);
+            host = nullptr; bytes = 0;
+            if ((e = hipHostMalloc((void**)&host, n, hipHostMallocDefault)) != hipSuccess) return e;
+            bytes = n;
+        }
+        memcpy(host, src, n);
+        return hipSuccess;
+    }
+    hipError_t done(hipStream_t st) { return hipEventRecord(ev, st); }
+    void release() { if (host) (void)hipHostFree(host); if (ev) (void)hipEventDestroy(ev); host = nullptr; bytes = 0; ev = nullptr; }
+};
+
+// ---- frame products -----------------------------------------------------------------------------------------------------------------------------------
+// What is made of a finished frame on request: the display image (idkptPresent, host_readback.hpp), the bloom chains (idkptBloom, host_bloom.hpp), the denoised image
+// (idkptDenoise / idkptUploadDenoised, host_denoise.hpp), the noise estimate and the moments images it reads (idkptEstimateNoise, host_noise.hpp).  Their life cycle is
+// stated HERE and nowhere else: the buffers belong to a ring slot and a frame size; they are made at the slot's first use (a context that never asks pays nothing), every
+// buffer ends in GUARD_BYTES of 0xA5 that no kernel writes (include/idkpt.h: what a host or a test looks at to see that nothing ran past the payload); every resize releases
+// them (alloc_frame_impl -> release_all), idkptSetPresentationSize releases those that have the presentation size, idkptSetMaxBatch keeps them (alloc_frame_keep_images moves
+// the owner aside), idkptDestroy releases them.  To add a product: a slot struct with release(), a vector of it in FrameProducts, a line in release_all (and one in
+// release_presentation_sized if it has the presentation size).
+#define GUARD_BYTES 64
+struct GuardedBuf {
+    DevBuf mem; size_t bytes = 0;                          // bytes: the payload in front of the guard
+    // reallocates (grow only) and rewrites the guard only when the payload size differs or nothing is allocated: a smaller payload moves the guard and keeps the allocation
+    hipError_t ensure(hipStream_t st, size_t n)
+    {
+        if (mem.p && bytes == n) return hipSuccess;
+        hipError_t e = mem.ensure(n + GUARD_BYTES);
+        if (e == hipSuccess) e = hipMemsetAsync((char*)mem.p + n, 0xA5, GUARD_BYTES, st);
+        if (e == hipSuccess) bytes = n;
+        return e;
+    }
+    void release() { mem.release(); bytes = 0; }
+    template <class T> T* as() const { return (T*)mem.p; }
+};
+
+// idkptPresent: the display image of one ring slot and its format (enum idkpt_display_format; -1: not presented since the last resize)
+struct DisplaySlot {
+    GuardedBuf image; int format = -1;
+    void release() { image.release(); format = -1; }
+};
+
+// idkptBloom: RGBA16F levels of the down and the up chain (one behind the other, level 0 first), the expanded RGBA32F image, and what the last bloom made of them
 struct BloomSlot {
-    DevBuf down, up, out; size_t downBytes = 0, upBytes = 0, outBytes = 0;   // (bytes in front of each buffer's guard)
+    GuardedBuf down, up, out;
     int levels = 0, w0 = 0, h0 = 0; bool valid = false;                      // valid: bloomed since the last resize
     bool direct = false;                                                     // down pass 0 of the last bloom fetched from memory (k_bloom_down0_direct) instead of staging tiles
-    void release() { down.release(); up.release(); out.release(); downBytes = upBytes = outBytes = 0; valid = false; }
+    void release() { down.release(); up.release(); out.release(); valid = false; }
 };
 
-// idkptDenoise / idkptUploadDenoised (host_denoise.hpp): the buffers of one ring slot — the denoised RGBA32F image and the two RGBA32F images the iterations alternate
-// between — and how the last idkptDenoise reached each iteration's taps
+// idkptDenoise / idkptUploadDenoised: the denoised RGBA32F image, the two RGBA32F images the iterations alternate between, and how the last idkptDenoise reached each iteration's taps
 struct DenoiseSlot {
-    DevBuf out, ping[2]; size_t outBytes = 0, pingBytes[2] = {0, 0};         // (bytes in front of each buffer's guard)
+    GuardedBuf out, ping[2];
     bool valid = false;                                                      // holds a denoised image (filtered or uploaded) since the last resize
     int iterations = 0; uint8_t route[8] = {0};                              // of the last idkptDenoise (0 iterations: the image was uploaded); enum idkpt_denoise_route
-    void release() { out.release(); ping[0].release(); ping[1].release(); outBytes = pingBytes[0] = pingBytes[1] = 0; valid = false; iterations = 0; }
+    void release() { out.release(); ping[0].release(); ping[1].release(); valid = false; iterations = 0; }
 };
 
-// idkptEstimateNoise (host_noise.hpp): the buffers of one ring slot — two floats (mean, max) per 8 x 8 tile and the idkpt_noise_summary record
+// idkptEstimateNoise: two floats (mean, max) per 8 x 8 tile and the idkpt_noise_summary record
 struct NoiseSlot {
-    DevBuf tiles, summary; size_t tileBytes = 0, summaryBytes = 0;           // (bytes in front of each buffer's guard)
+    GuardedBuf tiles, summary;
     int tilesX = 0, tilesY = 0; bool valid = false;                          // valid: holds an estimate since the last resize
-    void release() { tiles.release(); summary.release(); tileBytes = summaryBytes = 0; valid = false; }
+    void release() { tiles.release(); summary.release(); valid = false; }
+};
+
+static bool slot_holds(const DisplaySlot& s) { return s.format >= 0; }
+template <class S> static bool slot_holds(const S& s) { return s.valid; }
+
+struct FrameProducts {
+    std::vector<DisplaySlot> display; std::vector<BloomSlot> bloom; std::vector<DenoiseSlot> denoise; std::vector<NoiseSlot> noise;
+    DevBuf moments;              // idkptSetNoiseEstimate: the moments images (m1, m2, 0, 1) of ALL ring slots in one allocation, each followed by its guard (host_noise.hpp noise_moments_ensure)
+    template <class S> static void drop(std::vector<S>& v) { for (S& s : v) s.release(); v.clear(); }
+    void release_noise() { drop(noise); moments.release(); }
+    void release_presentation_sized() { drop(display); drop(bloom); }
+    void release_all() { release_presentation_sized(); drop(denoise); release_noise(); }
+    // the record of a ring slot that is about to be made: the vector gets the ring's size at its first use after a release
+    template <class S> static S& slot(std::vector<S>& v, int ringSize, int slot) { if (v.size() != (size_t)ringSize) { drop(v); v.resize(ringSize); } return v[slot]; }
 };
 
 // Tuning / test options (idkptSetDeveloperOption; none is part of the reference's interface and results are bit-identical under all of them:
@@ -198,22 +264,18 @@ struct dev_ctx {
     uint8_t lastSlots[VB_COUNT] = {0}; bool lastMulti = false;   // ... the one set of slots of a single-version batch, or "per sample: verTab"
     DevBuf verTab; PinnedStage verStage;               // per-sample version table of the batch being launched, and its staging
     char* hStage = nullptr; hipEvent_t evStage[4] = {nullptr, nullptr, nullptr, nullptr}; int stageNext = 0;   // pinned ring for small host -> device updates (joint matrices, transforms): no stream synchronisation per call
-    char* hSkyStage = nullptr; size_t hSkyStageBytes = 0; hipEvent_t evSkyStage = nullptr;   // pinned staging of the host faces idkptUpdateSky uploads (its copy is asynchronous: the call does not wait for the stream); the event = the last copy that read it
+    PinnedUpload skyStage;                            // the host faces idkptUpdateSky uploads
     hipEvent_t evSky = nullptr;                       // multi-device contexts: this member's last write to / last peer read of its sky (idkpt_api.hpp idkptUpdateSky)
     int (*groupFlushAll)(void* user) = nullptr;      // member of a multi-device context: launches what ALL members have queued (a member never flushes on its own)
     // wavefront state
     DevBuf pmList;                                       // the first bounce's work list in pixel-major order (k_shade_first)
     DevBuf trRec, contFlag, blockSums, rayO, rayT, rayR, aovA, aovN, hit, hitCost, primHit, queue[2], keys[2], keysTmp, sortKeys, sortVals, contMask, waveCounts, counts, work, sortHist, counters64;
     DevBuf img[3];
-    std::vector<DevBuf> disp; std::vector<int> dispFmt;   // idkptPresent: the display image of every ring slot (allocated at the first present of the slot) and its format (enum idkpt_display_format; -1: not presented since the last resize)
-    std::vector<BloomSlot> bloom;   // idkptBloom: per ring slot, allocated at the slot's first bloom
+    FrameProducts products;         // display, bloom, denoised image, noise estimate: everything that belongs to a ring slot and a frame size and is made on request
     int presW = 0, presH = 0;       // idkptSetPresentationSize: the size of the display and bloom images (0, 0: the render size); a state of its own, kept by every resize
-    std::vector<DenoiseSlot> denoise;   // idkptDenoise / idkptUploadDenoised: per ring slot, allocated at the slot's first use
-    int resultSource = 0;               // idkptSetResultSource (enum idkpt_result_source): what IDKPT_IMAGE_RESULT means to idkptPresent and idkptBloom; a state of its own, kept by every resize
-    char* hDenoiseStage = nullptr; size_t hDenoiseStageBytes = 0; hipEvent_t evDenoiseStage = nullptr;   // pinned staging of idkptUploadDenoised's host image (the pattern of hSkyStage)
-    int noiseOn = 0;                    // idkptSetNoiseEstimate: FinalDraw folds every sample's luminance into the moments images as well; a state of its own, kept by every resize
-    DevBuf noiseMom;                    // ... the moments images (m1, m2, 0, 1) of all ring slots, each followed by its guard bytes (host_noise.hpp); allocated at first use
-    std::vector<NoiseSlot> noise;       // idkptEstimateNoise: per ring slot, allocated at the slot's first estimate
+    int resultSource = 0;           // idkptSetResultSource (enum idkpt_result_source): what IDKPT_IMAGE_RESULT means to idkptPresent and idkptBloom; a state of its own, kept by every resize
+    PinnedUpload denoiseStage;      // idkptUploadDenoised's host image
+    int noiseOn = 0;                // idkptSetNoiseEstimate: FinalDraw folds every sample's luminance into the moments images as well; a state of its own, kept by every resize
     DevBuf camTab;                                       // per-sample cameras of the batch being launched (ring mode)
     int rowLimit = 0x7fffffff;                           // idkptSetRowRange: at most this many local rows
     idkpt_bounce_exchange_fn exchangeFn = nullptr; void* exchangeUser = nullptr;   // exact multi-GPU deep paths (idkptSetBounceExchange)
@@ -268,6 +330,27 @@ static int fail(dev_ctx* c, int code, const std::string& msg) { if (c) { c->last
 // (a failed runtime call leaves its code in the thread's last-error slot: reset it, or the next hipGetLastError() check would report it again)
 #define HIPC(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { (void)hipGetLastError(); return fail(ctx, IDKPT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); } } while (0)
 #define REQUIRE(cond, msg) do { if (!(cond)) return fail(ctx, IDKPT_ERR_INVALID_ARGUMENT, msg); } while (0)
+
+// ---- what a context holds of the frame, and the size it presents (idkptSetPresentationSize) -----------------------------------------------------------------
+// The presentation size is the size of the display image and of bloom's chain and expanded image.  (0, 0) follows the render size.  While it equals the render size
+// idkptPresent / idkptBloom run exactly what they ran before there was one; when it differs (present_scaled) the scaled kernels run, on one device with the whole frame only.
+static bool holds_whole_frame(const dev_ctx* ctx) { return ctx->rowMod == 1 && ctx->rowRem == 0 && ctx->rows == ctx->H; }
+static bool owns_whole_frame(const dev_ctx* ctx) { return !ctx->grouped && holds_whole_frame(ctx); }   // ... and is no member of a multi-device context: what a global filter needs
+static int pres_w(const dev_ctx* ctx) { return ctx->presW ? ctx->presW : ctx->W; }
+static int pres_h(const dev_ctx* ctx) { return ctx->presW ? ctx->presH : ctx->H; }
+static bool present_scaled(const dev_ctx* ctx) { return ctx->presW && (ctx->presW != ctx->W || ctx->presH != ctx->H); }
+static size_t display_texel_bytes(int format) { return format == IDKPT_DISPLAY_RGBA32F ? 16 : 4; }
+static size_t display_texels(const dev_ctx* ctx) { return present_scaled(ctx) ? (size_t)ctx->presW * ctx->presH : (size_t)ctx->W * ctx->rows; }
+
+// The record of ring slot `slot` (-1: the current one) of a frame product, for the calls that READ it; INVALID_OPERATION with who + `none` when the slot holds none since the last resize
+template <class S> static int32_t slot_of(dev_ctx* ctx, std::vector<S>& v, const char* who, int32_t slot, const char* none, S** out)
+{
+    REQUIRE(slot >= -1 && slot < ctx->ringSize, std::string(who) + ": slot outside the frame ring (-1: the current slot)");
+    if (slot < 0) slot = ctx->curSlot;
+    if ((size_t)slot >= v.size() || !slot_holds(v[slot])) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, std::string(who) + none);
+    *out = &v[slot];
+    return IDKPT_OK;
+}
 
 // rows y of the image with (y >> bandLog2) % mod == rem (bandLog2 = 0: y % mod == rem; mod = 1: the rows from rem on)
 static int local_rows(int H, int mod, int rem, int bandLog2 = 0)

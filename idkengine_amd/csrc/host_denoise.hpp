@@ -1,26 +1,18 @@
 // host_denoise.hpp — idkptDenoise / idkptUploadDenoised / idkptDownloadDenoised / idkptGetDenoisedDevicePtr / idkptGetDenoiseRoute / idkptSetResultSource: the denoised
 // image of a ring slot (kernels: kernels_denoise.hpp; the contract: include/idkpt.h).  Part of the single translation unit idkpt.hip (included there, in this order).
-// Behaves as idkptBloom does (host_bloom.hpp): queued samples are launched first, nothing but the download waits for the GPU, buffers belong to a ring slot and a frame
-// size — the denoised image and the two images the iterations alternate between, all RGBA32F of the render size —, are allocated at the slot's first use, released by
-// alloc_frame_impl, kept by idkptSetMaxBatch, and each is followed by DENOISE_GUARD_BYTES of 0xA5 that nothing writes.
+// Queued samples are launched first, nothing but the download waits for the GPU.  A frame product (host_context.hpp, "frame products": the life cycle of the buffers): the
+// denoised image and the two images the iterations alternate between, all RGBA32F of the render size.
 // One device, the whole frame: the taps of iteration i reach 2 * 2^i rows, a shard of the rows would need halos as tall as that.
 #pragma once
 
-#define DENOISE_GUARD_BYTES 64
 static int denoise_route(int spacing) { return spacing <= denoisek::MAX_TILE_SPACING ? IDKPT_DENOISE_ROUTE_TILED : IDKPT_DENOISE_ROUTE_DIRECT; }
 // what every call that makes or reads a denoised image needs of the context, after its arguments were checked
 static int32_t denoise_scope(dev_ctx* ctx, const char* who)
 {
     if (ctx->W <= 0 || !ctx->frameOk) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, std::string(who) + ": no frame buffers (idkptSetSize not called)");
-    if (ctx->grouped || !holds_whole_frame(ctx)) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, std::string(who) + ": the context holds a shard of the rows (idkptSetRowSharding / idkptSetRowBands / idkptSetRowRange) or is a member of a multi-device context; the denoised image needs the whole frame on one device");
+    if (!owns_whole_frame(ctx)) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, std::string(who) + ": the context holds a shard of the rows (idkptSetRowSharding / idkptSetRowBands / idkptSetRowRange) or is a member of a multi-device context; the denoised image needs the whole frame on one device");
     return IDKPT_OK;
 }
-static DenoiseSlot& denoise_slot(dev_ctx* ctx, int slot)
-{
-    if (ctx->denoise.size() != (size_t)ctx->ringSize) { for (DenoiseSlot& s : ctx->denoise) s.release(); ctx->denoise.assign(ctx->ringSize, DenoiseSlot()); }
-    return ctx->denoise[slot];
-}
-
 static int32_t dev_Denoise(dev_ctx* ctx, int32_t slot, const idkpt_denoise* d)
 {
     if (!ctx || !d) return IDKPT_ERR_INVALID_ARGUMENT;
@@ -37,15 +29,15 @@ static int32_t dev_Denoise(dev_ctx* ctx, int32_t slot, const idkpt_denoise* d)
     { int rc = check_overflow(ctx); if (rc) return rc; }   // (no wait: see idkptGetFrameDevicePtr)
     const int W = ctx->W, H = ctx->H, n = d->Iterations;
     const size_t bytes = (size_t)W * H * 16;
-    DenoiseSlot& s = denoise_slot(ctx, slot);
+    DenoiseSlot& s = FrameProducts::slot(ctx->products.denoise, ctx->ringSize, slot);
     s.valid = false; s.iterations = 0;
-    { int rc = bloom_ensure(ctx, s.out, s.outBytes, bytes); if (rc) return rc; }
-    for (int k = 0; k < 2 && k < n - 1; k++) { int rc = bloom_ensure(ctx, s.ping[k], s.pingBytes[k], bytes); if (rc) return rc; }
+    HIPC(s.out.ensure(ctx->stream, bytes));
+    for (int k = 0; k < 2 && k < n - 1; k++) HIPC(s.ping[k].ensure(ctx->stream, bytes));
     const float4* albedo = image_ptr(ctx, IDKPT_IMAGE_ALBEDO, slot); const float4* normal = image_ptr(ctx, IDKPT_IMAGE_NORMAL, slot);
     const dim3 grid((unsigned)((W + denoisek::TILE - 1) / denoisek::TILE), (unsigned)((H + denoisek::TILE - 1) / denoisek::TILE));
     const float4* src = image_ptr(ctx, IDKPT_IMAGE_RESULT, slot);
     for (int i = 0; i < n; i++) {
-        float4* dst = i == n - 1 ? (float4*)s.out.p : (float4*)s.ping[i & 1].p;
+        float4* dst = (i == n - 1 ? s.out : s.ping[i & 1]).as<float4>();
         denoisek::Params p;
         p.W = W; p.H = H; p.s = 1 << i;
         p.invC = denoiset::inv_sigma2(d->ColorSigma, i); p.invA = denoiset::inv_sigma2(d->AlbedoSigma, 0); p.invN = denoiset::inv_sigma2(d->NormalSigma, 0);
@@ -63,7 +55,7 @@ static int32_t dev_Denoise(dev_ctx* ctx, int32_t slot, const idkpt_denoise* d)
 }
 
 // the host's own denoiser's output (the reference's denoisedTexture.Upload2D): the array is borrowed for the call only and the copy must not make the call wait for the
-// stream, so the bytes go through a pinned buffer of the context's own (the pattern of idkptUpdateSky: only the PREVIOUS upload's copy is waited for)
+// stream, so the bytes go through a pinned buffer of the context's own (PinnedUpload: only the PREVIOUS upload's copy is waited for)
 static int32_t dev_UploadDenoised(dev_ctx* ctx, int32_t slot, const float* rgba, size_t bytes)
 {
     if (!ctx || !rgba) return IDKPT_ERR_INVALID_ARGUMENT;
@@ -74,59 +66,39 @@ static int32_t dev_UploadDenoised(dev_ctx* ctx, int32_t slot, const float* rgba,
     if (slot < 0) slot = ctx->curSlot;
     HIPC(hipSetDevice(ctx->device));
     FLUSH_KEEP();
-    DenoiseSlot& s = denoise_slot(ctx, slot);
+    DenoiseSlot& s = FrameProducts::slot(ctx->products.denoise, ctx->ringSize, slot);
     s.valid = false; s.iterations = 0;
-    { int rc = bloom_ensure(ctx, s.out, s.outBytes, need); if (rc) return rc; }
-    if (!ctx->evDenoiseStage) HIPC(hipEventCreateWithFlags(&ctx->evDenoiseStage, hipEventDisableTiming));
-    else HIPC(hipEventSynchronize(ctx->evDenoiseStage));
-    if (ctx->hDenoiseStageBytes < need) {
-        if (ctx->hDenoiseStage) (void)hipHostFree(ctx->hDenoiseStage);
-        ctx->hDenoiseStage = nullptr; ctx->hDenoiseStageBytes = 0;
-        HIPC(hipHostMalloc((void**)&ctx->hDenoiseStage, need, hipHostMallocDefault));
-        ctx->hDenoiseStageBytes = need;
-    }
-    memcpy(ctx->hDenoiseStage, rgba, need);
-    HIPC(hipMemcpyAsync(s.out.p, ctx->hDenoiseStage, need, hipMemcpyHostToDevice, ctx->stream));
-    HIPC(hipEventRecord(ctx->evDenoiseStage, ctx->stream));
+    HIPC(s.out.ensure(ctx->stream, need));
+    HIPC(ctx->denoiseStage.stage(rgba, need));
+    HIPC(hipMemcpyAsync(s.out.mem.p, ctx->denoiseStage.host, need, hipMemcpyHostToDevice, ctx->stream));
+    HIPC(ctx->denoiseStage.done(ctx->stream));
     s.valid = true;
     return IDKPT_OK;
 }
 
-// the denoised image of a slot; INVALID_OPERATION when the slot holds none since the last resize
-static int32_t denoised_of(dev_ctx* ctx, const char* who, int32_t slot, DenoiseSlot** out)
-{
-    REQUIRE(slot >= -1 && slot < ctx->ringSize, std::string(who) + ": slot outside the frame ring (-1: the current slot)");
-    if (slot < 0) slot = ctx->curSlot;
-    if ((size_t)slot >= ctx->denoise.size() || !ctx->denoise[slot].valid) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, std::string(who) + ": the slot holds no denoised image since the last resize (idkptDenoise / idkptUploadDenoised)");
-    *out = &ctx->denoise[slot];
-    return IDKPT_OK;
-}
+#define DENOISED_NONE ": the slot holds no denoised image since the last resize (idkptDenoise / idkptUploadDenoised)"
 static int32_t dev_DownloadDenoised(dev_ctx* ctx, int32_t slot, float* rgba, size_t bytes)
 {
     if (!ctx || !rgba) return IDKPT_ERR_INVALID_ARGUMENT;
     DenoiseSlot* s = nullptr;
-    { int rc = denoised_of(ctx, "idkptDownloadDenoised", slot, &s); if (rc) return rc; }
-    REQUIRE(bytes == s->outBytes, "idkptDownloadDenoised: bytes must equal height*width*16");
-    HIPC(hipSetDevice(ctx->device));
-    FLUSH_KEEP();
-    HIPC(hipMemcpyAsync(rgba, s->out.p, s->outBytes, hipMemcpyDeviceToHost, ctx->stream));
-    SYNC_CHECKED();
-    return IDKPT_OK;
+    { int rc = slot_of(ctx, ctx->products.denoise, "idkptDownloadDenoised", slot, DENOISED_NONE, &s); if (rc) return rc; }
+    REQUIRE(bytes == s->out.bytes, "idkptDownloadDenoised: bytes must equal height*width*16");
+    return download_behind_queue(ctx, rgba, s->out.mem.p, bytes);
 }
 static int32_t dev_GetDenoisedDevicePtr(dev_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes)
 {
     if (!ctx || !outPtr) return IDKPT_ERR_INVALID_ARGUMENT;
     DenoiseSlot* s = nullptr;
-    { int rc = denoised_of(ctx, "idkptGetDenoisedDevicePtr", slot, &s); if (rc) return rc; }
-    *outPtr = s->out.p;
-    if (outBytes) *outBytes = s->outBytes;
+    { int rc = slot_of(ctx, ctx->products.denoise, "idkptGetDenoisedDevicePtr", slot, DENOISED_NONE, &s); if (rc) return rc; }
+    *outPtr = s->out.mem.p;
+    if (outBytes) *outBytes = s->out.bytes;
     return IDKPT_OK;
 }
 static int32_t dev_GetDenoiseRoute(dev_ctx* ctx, int32_t slot, int32_t iteration, int32_t* route)
 {
     if (!ctx || !route) return IDKPT_ERR_INVALID_ARGUMENT;
     DenoiseSlot* s = nullptr;
-    { int rc = denoised_of(ctx, "idkptGetDenoiseRoute", slot, &s); if (rc) return rc; }
+    { int rc = slot_of(ctx, ctx->products.denoise, "idkptGetDenoiseRoute", slot, DENOISED_NONE, &s); if (rc) return rc; }
     REQUIRE(iteration >= 0 && iteration < s->iterations, "idkptGetDenoiseRoute: iteration outside the slot's last idkptDenoise (an uploaded image has none)");
     *route = s->route[iteration];
     return IDKPT_OK;
@@ -136,7 +108,7 @@ static int32_t dev_SetResultSource(dev_ctx* ctx, int32_t source)
 {
     if (!ctx) return IDKPT_ERR_INVALID_ARGUMENT;
     REQUIRE(source == IDKPT_RESULT_NOISY || source == IDKPT_RESULT_DENOISED, "idkptSetResultSource: source must be IDKPT_RESULT_NOISY or IDKPT_RESULT_DENOISED");
-    if (source == IDKPT_RESULT_DENOISED && (ctx->grouped || !holds_whole_frame(ctx)))
+    if (source == IDKPT_RESULT_DENOISED && !owns_whole_frame(ctx))
         return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptSetResultSource: the denoised image needs the whole frame on one device; this context holds a shard of the rows or is a member of a multi-device context");
     ctx->resultSource = source;
     return IDKPT_OK;

@@ -32,16 +32,8 @@ static int alloc_frame_impl(dev_ctx* ctx)
     // a pixel-major batch leave the bytes of its sky-classified tiles unwritten: whatever they hold from an earlier batch (0, 2, 4) cannot enqueue a ray, and whether such a
     // pixel is "culled per tile" is read from the batch's tile classes, which take precedence over the byte (k_regen_culled).
     ctx->accum.assign(ctx->ringSize, 0u); ctx->curSlot = 0; ctx->ringStarted = false;
-    for (DevBuf& b : ctx->disp) b.release();                       // display images (idkptPresent) belong to a frame size and a ring: re-made at their next use
-    ctx->disp.clear(); ctx->dispFmt.clear();
-    for (BloomSlot& s : ctx->bloom) s.release();                   // ... and so do the bloom chains (idkptBloom)
-    ctx->bloom.clear();
-    for (DenoiseSlot& s : ctx->denoise) s.release();               // ... and the denoised images (idkptDenoise / idkptUploadDenoised)
-    ctx->denoise.clear();
-    ctx->noiseMom.release();                                       // ... the moments images (idkptSetNoiseEstimate; zeroed again at their next use) and the estimates made of them
-    for (NoiseSlot& s : ctx->noise) s.release();
-    ctx->noise.clear();
-    if (ctx->grouped || ctx->rowMod != 1 || ctx->rowRem != 0 || ctx->rows != ctx->H) ctx->noiseOn = 0;   // a shard of the rows: the estimate needs the whole frame (host_noise.hpp)
+    ctx->products.release_all();                                   // they belong to a frame size and a ring: re-made (the moments images zeroed again) at their next use
+    if (!owns_whole_frame(ctx)) ctx->noiseOn = 0;                  // a shard of the rows: the estimate needs the whole frame (host_noise.hpp)
     return IDKPT_OK;
 }
 
@@ -54,12 +46,9 @@ static int alloc_frame_keep_images(dev_ctx* ctx)
     const size_t N = (size_t)ctx->W * ctx->rows;
     DevBuf saved[3];
     for (int i = 0; i < 3; i++) { saved[i] = ctx->img[i]; ctx->img[i] = DevBuf(); }
-    std::vector<DevBuf> disp; std::vector<int> dispFmt; disp.swap(ctx->disp); dispFmt.swap(ctx->dispFmt);   // (the display images stay as well: same size, same ring)
-    std::vector<BloomSlot> bloom; bloom.swap(ctx->bloom);                                                   // (and the bloom chains)
-    std::vector<DenoiseSlot> denoise; denoise.swap(ctx->denoise);                                           // (and the denoised images)
-    DevBuf noiseMom = ctx->noiseMom; ctx->noiseMom = DevBuf(); std::vector<NoiseSlot> noise; noise.swap(ctx->noise);   // (and the moments images with their estimates)
+    FrameProducts products = std::move(ctx->products); ctx->products = FrameProducts();   // (the frame products stay as well: same size, same ring)
     int rc = alloc_frame(ctx);
-    ctx->disp.swap(disp); ctx->dispFmt.swap(dispFmt); ctx->bloom.swap(bloom); ctx->denoise.swap(denoise); ctx->noiseMom = noiseMom; ctx->noise.swap(noise);
+    ctx->products = std::move(products);
     // The restore is ordered on the context's stream, behind the zero-fill alloc_frame_impl queued there: the stream is non-blocking, so
     // a null-stream copy would be unordered against that fill (the fill could land after the restore and wipe the accumulation).
     hipError_t e = hipSuccess;
@@ -89,6 +78,15 @@ static int finish_deferred(dev_ctx* ctx);
 static int flush_any(dev_ctx* ctx);
 #define FLUSH() do { int _rc = flush_any(ctx); if (_rc) return _rc; _rc = finish_deferred(ctx); if (_rc) return _rc; } while (0)
 #define FLUSH_KEEP() do { int _rc = flush_any(ctx); if (_rc) return _rc; } while (0)
+// a download of a frame product (a buffer no launch moves): the queued samples are launched, the copy is ordered behind them, the call waits — in this order
+static int32_t download_behind_queue(dev_ctx* ctx, void* dst, const void* src, size_t bytes)
+{
+    HIPC(hipSetDevice(ctx->device));
+    FLUSH_KEEP();
+    HIPC(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    SYNC_CHECKED();
+    return IDKPT_OK;
+}
 
 // ---- scene versions -------------------------------------------------------------------------------------------------------------------------------
 // A scene update (skinning, refit, TLAS rebuild, a patched transform) used to launch every queued sample first: the kernels of a batch read "the" scene, so

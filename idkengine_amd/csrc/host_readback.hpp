@@ -190,19 +190,8 @@ static int32_t dev_SetStream(dev_ctx* ctx, void* hipStream)
 static int32_t dev_GetStream(dev_ctx* ctx, void** out) { if (!ctx || !out) return IDKPT_ERR_INVALID_ARGUMENT; *out = (void*)ctx->stream; return IDKPT_OK; }
 
 // ---- the display image (idkptPresent / idkptDownloadDisplay / idkptGetDisplayDevicePtr; kernels_present.hpp) ------------------------------------------------------------
-// One buffer per ring slot, allocated at the slot's first present (a context that never presents pays nothing) and released with the frame buffers (alloc_frame_impl).
-// Every buffer ends with DISPLAY_GUARD_BYTES of 0xA5 right behind the image that no kernel writes (include/idkpt.h: what a host or a test can look at to see that a
-// row tail never ran past the image).
-#define DISPLAY_GUARD_BYTES 64
-static size_t display_texel_bytes(int format) { return format == IDKPT_DISPLAY_RGBA32F ? 16 : 4; }
-// The presentation size (idkptSetPresentationSize): the size of the display image and of bloom's chain and expanded image.  (0, 0) follows the render size.  While it equals
-// the render size idkptPresent / idkptBloom run exactly what they ran before there was one; when it differs (present_scaled) the scaled kernels run, on one device with the
-// whole frame only.
-static int pres_w(const dev_ctx* ctx) { return ctx->presW ? ctx->presW : ctx->W; }
-static int pres_h(const dev_ctx* ctx) { return ctx->presW ? ctx->presH : ctx->H; }
-static bool present_scaled(const dev_ctx* ctx) { return ctx->presW && (ctx->presW != ctx->W || ctx->presH != ctx->H); }
-static bool holds_whole_frame(const dev_ctx* ctx) { return ctx->rowMod == 1 && ctx->rowRem == 0 && ctx->rows == ctx->H; }
-static size_t display_texels(const dev_ctx* ctx) { return present_scaled(ctx) ? (size_t)ctx->presW * ctx->presH : (size_t)ctx->W * ctx->rows; }
+// One DisplaySlot per ring slot; its life cycle is that of every frame product (host_context.hpp, "frame products").  The guard sits right behind the image of the
+// slot's current format: a present in another format moves it, and the smaller format reuses the larger allocation.
 static int32_t dev_SetPresentationSize(dev_ctx* ctx, int32_t width, int32_t height)
 {
     if (!ctx) return IDKPT_ERR_INVALID_ARGUMENT;
@@ -210,10 +199,7 @@ static int32_t dev_SetPresentationSize(dev_ctx* ctx, int32_t width, int32_t heig
     if (width == ctx->presW && height == ctx->presH) return IDKPT_OK;
     HIPC(hipSetDevice(ctx->device));
     // neither the images nor the accumulation are touched, nothing queued is launched: only what has the presentation size goes, and is re-made at its next use
-    for (DevBuf& b : ctx->disp) b.release();
-    ctx->disp.clear(); ctx->dispFmt.clear();
-    for (BloomSlot& s : ctx->bloom) s.release();
-    ctx->bloom.clear();
+    ctx->products.release_presentation_sized();
     ctx->presW = width; ctx->presH = height;
     return IDKPT_OK;
 }
@@ -228,8 +214,8 @@ static int32_t dev_GetPresentationSize(dev_ctx* ctx, int32_t* width, int32_t* he
 // to idkptPresent and idkptBloom — and to nothing else.  source_missing: the call has to refuse (no denoised image in the slot since the last resize); source_ptr: the image
 // those two calls read.  Images 1 and 2 never look at the source.
 static bool source_denoised(const dev_ctx* ctx, int image) { return ctx->resultSource == IDKPT_RESULT_DENOISED && image == IDKPT_IMAGE_RESULT; }
-static bool source_missing(const dev_ctx* ctx, int image, int slot) { return source_denoised(ctx, image) && ((size_t)slot >= ctx->denoise.size() || !ctx->denoise[slot].valid); }
-static const float4* source_ptr(dev_ctx* ctx, int image, int slot) { return source_denoised(ctx, image) ? (const float4*)ctx->denoise[slot].out.p : image_ptr(ctx, image, slot); }
+static bool source_missing(const dev_ctx* ctx, int image, int slot) { return source_denoised(ctx, image) && ((size_t)slot >= ctx->products.denoise.size() || !ctx->products.denoise[slot].valid); }
+static const float4* source_ptr(dev_ctx* ctx, int image, int slot) { return source_denoised(ctx, image) ? ctx->products.denoise[slot].out.as<const float4>() : image_ptr(ctx, image, slot); }
 // everything idkptPresent refuses before anything is launched (shared with the multi-device layer)
 static int32_t present_validate(dev_ctx* ctx, int32_t slot, int32_t image, const idkpt_tonemap* tm, int32_t format)
 {
@@ -239,7 +225,7 @@ static int32_t present_validate(dev_ctx* ctx, int32_t slot, int32_t image, const
     auto fin = [](float v) { return v - v == 0.0f; };
     REQUIRE(fin(tm->Exposure) && fin(tm->Saturation) && fin(tm->Linear) && fin(tm->Peak) && fin(tm->Compression), "idkptPresent: Exposure, Saturation, Linear, Peak and Compression must be finite");
     if (ctx->W <= 0 || !ctx->frameOk) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptPresent: no frame buffers (idkptSetSize not called)");
-    if (present_scaled(ctx) && (ctx->grouped || !holds_whole_frame(ctx)))
+    if (present_scaled(ctx) && !owns_whole_frame(ctx))
         return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptPresent: a presentation size other than the render size (idkptSetPresentationSize) needs one device that holds the whole frame; this context is a member of a multi-device context or holds a shard of the rows");
     return IDKPT_OK;
 }
@@ -253,11 +239,10 @@ static int32_t dev_Present(dev_ctx* ctx, int32_t slot, int32_t image, const idkp
     FLUSH_KEEP();                                        // stream-ordered behind what was queued; the frame is complete without the deferred bounce's continuation (finish_deferred)
     { int rc = check_overflow(ctx); if (rc) return rc; }   // (no wait: see idkptGetFrameDevicePtr)
     const bool scaled = present_scaled(ctx);
-    const size_t imageBytes = display_texels(ctx) * display_texel_bytes(format);
-    if (ctx->disp.size() != (size_t)ctx->ringSize) { ctx->disp.resize(ctx->ringSize); ctx->dispFmt.assign(ctx->ringSize, -1); }
-    DevBuf& buf = ctx->disp[slot];
-    if (!buf.p || buf.bytes < imageBytes + DISPLAY_GUARD_BYTES) { ctx->dispFmt[slot] = -1; HIPC(buf.ensure(imageBytes + DISPLAY_GUARD_BYTES)); }
-    if (ctx->dispFmt[slot] != format) HIPC(hipMemsetAsync((char*)buf.p + imageBytes, 0xA5, DISPLAY_GUARD_BYTES, ctx->stream));   // (the guard sits right behind the image of THIS format)
+    DisplaySlot& s = FrameProducts::slot(ctx->products.display, ctx->ringSize, slot);
+    s.format = -1;                                       // (not presented until the launch below went through)
+    HIPC(s.image.ensure(ctx->stream, display_texels(ctx) * display_texel_bytes(format)));
+    void* const buf = s.image.as<void>();
     presentk::Params p;
     presentk::present_setup(tm->Exposure, tm->Compression, &p);
     p.saturation = tm->Saturation; p.linear = tm->Linear; p.peak = tm->Peak; p.doTonemap = tm->DoTonemapAndSrgbTransform != 0;
@@ -265,42 +250,31 @@ static int32_t dev_Present(dev_ctx* ctx, int32_t slot, int32_t image, const idkp
     if (scaled) { p.W = ctx->presW; p.rows = ctx->presH; }      // (the whole frame on this device: present_validate)
     const uint32_t threads = (uint32_t)(((size_t)p.W + 3) / 4 * p.rows);
     if (threads && scaled) {
-        with_flag(format == IDKPT_DISPLAY_RGBA32F, [&](auto F32) { launch(k_present_scaled<F32>, dim3((threads + 255u) / 256u), dim3(256), 0, ctx->stream, source_ptr(ctx, image, slot), ctx->W, ctx->H, (const float4*)dAdd0, (const float4*)dAdd1, buf.p, p); });
+        with_flag(format == IDKPT_DISPLAY_RGBA32F, [&](auto F32) { launch(k_present_scaled<F32>, dim3((threads + 255u) / 256u), dim3(256), 0, ctx->stream, source_ptr(ctx, image, slot), ctx->W, ctx->H, (const float4*)dAdd0, (const float4*)dAdd1, buf, p); });
         HIPC(hipGetLastError());
     } else if (threads) {
-        with_flag(format == IDKPT_DISPLAY_RGBA32F, [&](auto F32) { launch(k_present<F32>, dim3((threads + 255u) / 256u), dim3(256), 0, ctx->stream, source_ptr(ctx, image, slot), (const float4*)dAdd0, (const float4*)dAdd1, buf.p, p); });
+        with_flag(format == IDKPT_DISPLAY_RGBA32F, [&](auto F32) { launch(k_present<F32>, dim3((threads + 255u) / 256u), dim3(256), 0, ctx->stream, source_ptr(ctx, image, slot), (const float4*)dAdd0, (const float4*)dAdd1, buf, p); });
         HIPC(hipGetLastError());
     }
-    ctx->dispFmt[slot] = format;
+    s.format = format;
     return IDKPT_OK;
 }
-// the last presented image of a slot: *outFormat its format, *outBytes localRows * width * (4 | 16); INVALID_OPERATION when the slot was not presented since the last resize
-static int32_t display_of(dev_ctx* ctx, const char* who, int32_t slot, int32_t* outSlot, size_t* outBytes)
-{
-    REQUIRE(slot >= -1 && slot < ctx->ringSize, std::string(who) + ": slot outside the frame ring (-1: the current slot)");
-    if (slot < 0) slot = ctx->curSlot;
-    if ((size_t)slot >= ctx->dispFmt.size() || ctx->dispFmt[slot] < 0) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, std::string(who) + ": the slot was not presented since the last resize (idkptPresent)");
-    *outSlot = slot; *outBytes = display_texels(ctx) * display_texel_bytes(ctx->dispFmt[slot]);
-    return IDKPT_OK;
-}
+// the last presented image of a slot: localRows * width * (4 | 16) bytes, rows and width of the presentation size where one is set
+#define DISPLAY_NONE ": the slot was not presented since the last resize (idkptPresent)"
 static int32_t dev_DownloadDisplay(dev_ctx* ctx, int32_t slot, void* dst, size_t bytes)
 {
     if (!ctx || !dst) return IDKPT_ERR_INVALID_ARGUMENT;
-    size_t need = 0;
-    { int rc = display_of(ctx, "idkptDownloadDisplay", slot, &slot, &need); if (rc) return rc; }
-    REQUIRE(bytes == need, "idkptDownloadDisplay: bytes must equal localRows*width*4 (RGBA8) or localRows*width*16 (RGBA32F), rows and width of the presentation size where one is set");
-    HIPC(hipSetDevice(ctx->device));
-    FLUSH_KEEP();
-    HIPC(hipMemcpyAsync(dst, ctx->disp[slot].p, need, hipMemcpyDeviceToHost, ctx->stream));
-    SYNC_CHECKED();
-    return IDKPT_OK;
+    DisplaySlot* s = nullptr;
+    { int rc = slot_of(ctx, ctx->products.display, "idkptDownloadDisplay", slot, DISPLAY_NONE, &s); if (rc) return rc; }
+    REQUIRE(bytes == s->image.bytes, "idkptDownloadDisplay: bytes must equal localRows*width*4 (RGBA8) or localRows*width*16 (RGBA32F), rows and width of the presentation size where one is set");
+    return download_behind_queue(ctx, dst, s->image.mem.p, bytes);
 }
 static int32_t dev_GetDisplayDevicePtr(dev_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes)
 {
     if (!ctx || !outPtr) return IDKPT_ERR_INVALID_ARGUMENT;
-    size_t need = 0;
-    { int rc = display_of(ctx, "idkptGetDisplayDevicePtr", slot, &slot, &need); if (rc) return rc; }
-    *outPtr = ctx->disp[slot].p;
-    if (outBytes) *outBytes = need;
+    DisplaySlot* s = nullptr;
+    { int rc = slot_of(ctx, ctx->products.display, "idkptGetDisplayDevicePtr", slot, DISPLAY_NONE, &s); if (rc) return rc; }
+    *outPtr = s->image.mem.p;
+    if (outBytes) *outBytes = s->image.bytes;
     return IDKPT_OK;
 }

@@ -129,13 +129,8 @@ static int32_t dev_Destroy(dev_ctx* ctx)
                      &ctx->counts, &ctx->work, &ctx->qwork, &ctx->radSave, &ctx->deferCount, &ctx->sortHist, &ctx->counters64, &ctx->bases, &ctx->img[0], &ctx->img[1], &ctx->img[2]};
     for (DevBuf* b : all) b->release();
     for (auto& t : ctx->texData) t.release();
-    for (DevBuf& b : ctx->disp) b.release();
-    for (BloomSlot& s : ctx->bloom) s.release();
-    for (DenoiseSlot& s : ctx->denoise) s.release();
-    ctx->noiseMom.release();
-    for (NoiseSlot& s : ctx->noise) s.release();
-    if (ctx->hDenoiseStage) (void)hipHostFree(ctx->hDenoiseStage);
-    if (ctx->evDenoiseStage) (void)hipEventDestroy(ctx->evDenoiseStage);
+    ctx->products.release_all();
+    ctx->denoiseStage.release(); ctx->skyStage.release();
     builder_scratch_free(ctx);
     if (ctx->hCounts) (void)hipHostFree(ctx->hCounts);
     if (ctx->hOverflow) (void)hipHostFree(ctx->hOverflow);
@@ -145,8 +140,6 @@ static int32_t dev_Destroy(dev_ctx* ctx)
     if (ctx->hBases) (void)hipHostFree(ctx->hBases);
     ctx->camStage.release(); ctx->verStage.release();
     if (ctx->hStage) (void)hipHostFree(ctx->hStage);
-    if (ctx->hSkyStage) (void)hipHostFree(ctx->hSkyStage);
-    if (ctx->evSkyStage) (void)hipEventDestroy(ctx->evSkyStage);
     if (ctx->evSky) (void)hipEventDestroy(ctx->evSky);
     for (int i = 0; i < 4; i++) if (ctx->evStage[i]) (void)hipEventDestroy(ctx->evStage[i]);
     if (ctx->evFrame[0]) (void)hipEventDestroy(ctx->evFrame[0]);
@@ -687,28 +680,20 @@ static int32_t dev_UpdateSky(dev_ctx* ctx, int32_t faceSize, int32_t format, con
     if (S == 0) { ctx->skySize = 0; return IDKPT_OK; }               // no sky: black (SampleSky)
     const size_t texels = (size_t)6 * S * S, srcBytes = texels * (format == IDKPT_TEXFMT_RGBA32F ? 16 : 4);
     // The host's array is borrowed for the call only and the copy must not make the call wait for the stream: the bytes go through a pinned buffer of the context's own
-    // (the pattern of staged_upload, one buffer of the size of the largest sky so far; only the PREVIOUS sky upload's copy is waited for, normally long finished).
-    if (!ctx->evSkyStage) HIPC(hipEventCreateWithFlags(&ctx->evSkyStage, hipEventDisableTiming));
-    else HIPC(hipEventSynchronize(ctx->evSkyStage));
-    if (ctx->hSkyStageBytes < srcBytes) {
-        if (ctx->hSkyStage) (void)hipHostFree(ctx->hSkyStage);
-        ctx->hSkyStage = nullptr; ctx->hSkyStageBytes = 0;
-        HIPC(hipHostMalloc((void**)&ctx->hSkyStage, srcBytes, hipHostMallocDefault));
-        ctx->hSkyStageBytes = srcBytes;
-    }
-    memcpy(ctx->hSkyStage, faces, srcBytes);
+    // (PinnedUpload: only the PREVIOUS sky upload's copy is waited for, normally long finished).
+    HIPC(ctx->skyStage.stage(faces, srcBytes));
     if (format == IDKPT_TEXFMT_RGBA32F) {
-        HIPC(hipMemcpyAsync(ctx->sky.p, ctx->hSkyStage, srcBytes, hipMemcpyHostToDevice, ctx->stream));
+        HIPC(hipMemcpyAsync(ctx->sky.p, ctx->skyStage.host, srcBytes, hipMemcpyHostToDevice, ctx->stream));
     } else {
         // 8-bit faces are staged on the device and expanded by one kernel, as the texture table's source formats are (texStage: free here — idkptUploadScene and idkptUpdateTexture
         // end with the stream idle, and an earlier expansion of this function is ordered before this copy on the stream; it is reallocated only after a synchronisation)
         { int rc = tex_srgb_lut(ctx); if (rc) return rc; }
         if (ctx->texStage.bytes < srcBytes) { HIPC(hipStreamSynchronize(ctx->stream)); HIPC(ctx->texStage.ensure(srcBytes)); }
-        HIPC(hipMemcpyAsync(ctx->texStage.p, ctx->hSkyStage, srcBytes, hipMemcpyHostToDevice, ctx->stream));
+        HIPC(hipMemcpyAsync(ctx->texStage.p, ctx->skyStage.host, srcBytes, hipMemcpyHostToDevice, ctx->stream));
         hipLaunchKernelGGL(k_sky_expand, dim3((unsigned)((texels + 255) / 256)), dim3(256), 0, ctx->stream, (const uint32_t*)ctx->texStage.p, ctx->sky.as<float4>(), (uint32_t)texels, (int)format, (const float*)ctx->srgbLut.as<float>());
         HIPC(hipGetLastError());
     }
-    HIPC(hipEventRecord(ctx->evSkyStage, ctx->stream));
+    HIPC(ctx->skyStage.done(ctx->stream));
     ctx->skySize = S;
     return IDKPT_OK;
 }

@@ -404,7 +404,6 @@ static int defer_last_bounce(Batch& b, int j, const uint32_t* q, const uint32_t*
     return IDKPT_OK;
 }
 
-static int noise_moments_ensure(dev_ctx* ctx); static float4* noise_moments_ptr(dev_ctx* ctx, int slot); static size_t noise_mom_stride(const dev_ctx* ctx);   // (host_noise.hpp)
 // FinalDraw (which also resets the batch counters for the next batch) and what the context remembers of the batch
 static int final_draw(Batch& b)
 {

@@ -51,11 +51,11 @@ using namespace ptd;
 #include "host_scene.hpp"
 #include "host_builder.hpp"
 #include "host_queries.hpp"
+#include "host_noise.hpp"
 #include "host_schedule.hpp"
 #include "host_readback.hpp"
 #include "host_bloom.hpp"
 #include "host_denoise.hpp"
-#include "host_noise.hpp"
 #include "host_options.hpp"
 #include "transport_rccl.hpp"
 

@@ -375,9 +375,9 @@ static int group_gather_device(idkpt_ctx* c, int image, int slot, void** outPtr,
 static int group_display_rows(idkpt_ctx* c, const char* who, int slot, std::vector<const void*>& srcs, size_t* outTexel)
 {
     for (dev_ctx* m : c->dev) {
-        int s = 0; size_t bytes = 0;
-        int rc = display_of(m, who, slot, &s, &bytes); if (rc) return mfail(c, m, rc);
-        srcs.push_back(m->disp[s].p); *outTexel = display_texel_bytes(m->dispFmt[s]);
+        DisplaySlot* s = nullptr;
+        int rc = slot_of(m, m->products.display, who, slot, DISPLAY_NONE, &s); if (rc) return mfail(c, m, rc);
+        srcs.push_back(s->image.mem.p); *outTexel = display_texel_bytes(s->format);
     }
     return IDKPT_OK;
 }
@@ -876,8 +876,10 @@ int32_t idkptGetDisplayDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size
     return group_gather_rows(c, srcs, texel, c->fullDisp, outPtr, outBytes);
 }
 
-// ---- bloom (host_bloom.hpp): one device, the whole frame — a global filter; a shard of the rows would need halos as wide as the chain
-#define BLOOM_ONE(who, call) do { if (!c) return IDKPT_ERR_INVALID_ARGUMENT; ONE(call); return gfail(c, IDKPT_ERR_INVALID_OPERATION, who ": bloom runs on one device with the whole frame; a multi-device context has none"); } while (0)
+// ---- what needs one device with the whole frame: a multi-device context refuses with who + why + "; a multi-device context has none"
+#define ONE_ONLY(who, why, call) do { if (!c) return IDKPT_ERR_INVALID_ARGUMENT; ONE(call); return gfail(c, IDKPT_ERR_INVALID_OPERATION, who why "; a multi-device context has none"); } while (0)
+// ---- bloom (host_bloom.hpp): a global filter; a shard of the rows would need halos as wide as the chain
+#define BLOOM_WHY ": bloom runs on one device with the whole frame"
 int32_t idkptBloom(idkpt_ctx* c, int32_t slot, int32_t image, const idkpt_bloom* bloom)
 {
     if (!c) return IDKPT_ERR_INVALID_ARGUMENT;
@@ -885,19 +887,19 @@ int32_t idkptBloom(idkpt_ctx* c, int32_t slot, int32_t image, const idkpt_bloom*
     if (present_scaled(c->dev[0])) return gfail(c, IDKPT_ERR_INVALID_OPERATION, "idkptBloom: a presentation size other than the render size (idkptSetPresentationSize) needs one device that holds the whole frame; a multi-device context has none");
     return gfail(c, IDKPT_ERR_INVALID_OPERATION, "idkptBloom: bloom runs on one device with the whole frame; a multi-device context has none");
 }
-int32_t idkptGetBloomChainDevicePtr(idkpt_ctx* c, int32_t slot, int32_t chain, void** outPtr, size_t* outBytes) { BLOOM_ONE("idkptGetBloomChainDevicePtr", dev_GetBloomChainDevicePtr(m, slot, chain, outPtr, outBytes)); }
-int32_t idkptGetBloomRoute(idkpt_ctx* c, int32_t slot, int32_t* route) { BLOOM_ONE("idkptGetBloomRoute", dev_GetBloomRoute(m, slot, route)); }
-int32_t idkptGetBloomInfo(idkpt_ctx* c, int32_t slot, int32_t* levels, int32_t* w0, int32_t* h0) { BLOOM_ONE("idkptGetBloomInfo", dev_GetBloomInfo(m, slot, levels, w0, h0)); }
-int32_t idkptDownloadBloom(idkpt_ctx* c, int32_t slot, int32_t chain, int32_t level, void* dst, size_t bytes) { BLOOM_ONE("idkptDownloadBloom", dev_DownloadBloom(m, slot, chain, level, dst, bytes)); }
-int32_t idkptGetBloomDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size_t* outBytes) { BLOOM_ONE("idkptGetBloomDevicePtr", dev_GetBloomDevicePtr(m, slot, outPtr, outBytes)); }
+int32_t idkptGetBloomChainDevicePtr(idkpt_ctx* c, int32_t slot, int32_t chain, void** outPtr, size_t* outBytes) { ONE_ONLY("idkptGetBloomChainDevicePtr", BLOOM_WHY, dev_GetBloomChainDevicePtr(m, slot, chain, outPtr, outBytes)); }
+int32_t idkptGetBloomRoute(idkpt_ctx* c, int32_t slot, int32_t* route) { ONE_ONLY("idkptGetBloomRoute", BLOOM_WHY, dev_GetBloomRoute(m, slot, route)); }
+int32_t idkptGetBloomInfo(idkpt_ctx* c, int32_t slot, int32_t* levels, int32_t* w0, int32_t* h0) { ONE_ONLY("idkptGetBloomInfo", BLOOM_WHY, dev_GetBloomInfo(m, slot, levels, w0, h0)); }
+int32_t idkptDownloadBloom(idkpt_ctx* c, int32_t slot, int32_t chain, int32_t level, void* dst, size_t bytes) { ONE_ONLY("idkptDownloadBloom", BLOOM_WHY, dev_DownloadBloom(m, slot, chain, level, dst, bytes)); }
+int32_t idkptGetBloomDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size_t* outBytes) { ONE_ONLY("idkptGetBloomDevicePtr", BLOOM_WHY, dev_GetBloomDevicePtr(m, slot, outPtr, outBytes)); }
 
 // ---- the denoised image (host_denoise.hpp): one device, the whole frame — the taps of the last iteration reach 2 * 2^(Iterations - 1) rows
-#define DENOISE_ONE(who, call) do { if (!c) return IDKPT_ERR_INVALID_ARGUMENT; ONE(call); return gfail(c, IDKPT_ERR_INVALID_OPERATION, who ": the denoised image needs the whole frame on one device; a multi-device context has none"); } while (0)
-int32_t idkptDenoise(idkpt_ctx* c, int32_t slot, const idkpt_denoise* denoise) { DENOISE_ONE("idkptDenoise", dev_Denoise(m, slot, denoise)); }
-int32_t idkptUploadDenoised(idkpt_ctx* c, int32_t slot, const float* rgba, size_t bytes) { DENOISE_ONE("idkptUploadDenoised", dev_UploadDenoised(m, slot, rgba, bytes)); }
-int32_t idkptDownloadDenoised(idkpt_ctx* c, int32_t slot, float* rgba, size_t bytes) { DENOISE_ONE("idkptDownloadDenoised", dev_DownloadDenoised(m, slot, rgba, bytes)); }
-int32_t idkptGetDenoisedDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size_t* outBytes) { DENOISE_ONE("idkptGetDenoisedDevicePtr", dev_GetDenoisedDevicePtr(m, slot, outPtr, outBytes)); }
-int32_t idkptGetDenoiseRoute(idkpt_ctx* c, int32_t slot, int32_t iteration, int32_t* outRoute) { DENOISE_ONE("idkptGetDenoiseRoute", dev_GetDenoiseRoute(m, slot, iteration, outRoute)); }
+#define DENOISE_WHY ": the denoised image needs the whole frame on one device"
+int32_t idkptDenoise(idkpt_ctx* c, int32_t slot, const idkpt_denoise* denoise) { ONE_ONLY("idkptDenoise", DENOISE_WHY, dev_Denoise(m, slot, denoise)); }
+int32_t idkptUploadDenoised(idkpt_ctx* c, int32_t slot, const float* rgba, size_t bytes) { ONE_ONLY("idkptUploadDenoised", DENOISE_WHY, dev_UploadDenoised(m, slot, rgba, bytes)); }
+int32_t idkptDownloadDenoised(idkpt_ctx* c, int32_t slot, float* rgba, size_t bytes) { ONE_ONLY("idkptDownloadDenoised", DENOISE_WHY, dev_DownloadDenoised(m, slot, rgba, bytes)); }
+int32_t idkptGetDenoisedDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size_t* outBytes) { ONE_ONLY("idkptGetDenoisedDevicePtr", DENOISE_WHY, dev_GetDenoisedDevicePtr(m, slot, outPtr, outBytes)); }
+int32_t idkptGetDenoiseRoute(idkpt_ctx* c, int32_t slot, int32_t iteration, int32_t* outRoute) { ONE_ONLY("idkptGetDenoiseRoute", DENOISE_WHY, dev_GetDenoiseRoute(m, slot, iteration, outRoute)); }
 // the result source: a multi-device context stays at IDKPT_RESULT_NOISY (its members never look at anything else)
 int32_t idkptSetResultSource(idkpt_ctx* c, int32_t source)
 {
@@ -910,7 +912,7 @@ int32_t idkptSetResultSource(idkpt_ctx* c, int32_t source)
 int32_t idkptGetResultSource(idkpt_ctx* c, int32_t* outSource) { if (!c || !outSource) return IDKPT_ERR_INVALID_ARGUMENT; return dev_GetResultSource(c->dev[0], outSource); }
 
 // ---- the noise estimate (host_noise.hpp): one device, the whole frame — a tile's moments live where its rows are.  A multi-device context stays switched off (its members never fold)
-#define NOISE_ONE(who, call) do { if (!c) return IDKPT_ERR_INVALID_ARGUMENT; ONE(call); return gfail(c, IDKPT_ERR_INVALID_OPERATION, who ": the noise estimate needs the whole frame on one device; a multi-device context has none"); } while (0)
+#define NOISE_WHY ": the noise estimate needs the whole frame on one device"
 int32_t idkptSetNoiseEstimate(idkpt_ctx* c, int32_t enable)
 {
     if (!c) return IDKPT_ERR_INVALID_ARGUMENT;
@@ -920,11 +922,11 @@ int32_t idkptSetNoiseEstimate(idkpt_ctx* c, int32_t enable)
     return IDKPT_OK;
 }
 int32_t idkptGetNoiseEstimate(idkpt_ctx* c, int32_t* outEnable) { if (!c || !outEnable) return IDKPT_ERR_INVALID_ARGUMENT; return dev_GetNoiseEstimate(c->dev[0], outEnable); }
-int32_t idkptEstimateNoise(idkpt_ctx* c, int32_t slot, const idkpt_noise* noise) { NOISE_ONE("idkptEstimateNoise", dev_EstimateNoise(m, slot, noise)); }
-int32_t idkptDownloadNoise(idkpt_ctx* c, int32_t slot, float* tiles, size_t bytes, idkpt_noise_summary* outSummary) { NOISE_ONE("idkptDownloadNoise", dev_DownloadNoise(m, slot, tiles, bytes, outSummary)); }
-int32_t idkptGetNoiseDevicePtr(idkpt_ctx* c, int32_t slot, void** outTiles, void** outSummary, size_t* outTileBytes) { NOISE_ONE("idkptGetNoiseDevicePtr", dev_GetNoiseDevicePtr(m, slot, outTiles, outSummary, outTileBytes)); }
-int32_t idkptDownloadMoments(idkpt_ctx* c, int32_t slot, float* rgba, size_t bytes) { NOISE_ONE("idkptDownloadMoments", dev_DownloadMoments(m, slot, rgba, bytes)); }
-int32_t idkptGetMomentsDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size_t* outBytes) { NOISE_ONE("idkptGetMomentsDevicePtr", dev_GetMomentsDevicePtr(m, slot, outPtr, outBytes)); }
+int32_t idkptEstimateNoise(idkpt_ctx* c, int32_t slot, const idkpt_noise* noise) { ONE_ONLY("idkptEstimateNoise", NOISE_WHY, dev_EstimateNoise(m, slot, noise)); }
+int32_t idkptDownloadNoise(idkpt_ctx* c, int32_t slot, float* tiles, size_t bytes, idkpt_noise_summary* outSummary) { ONE_ONLY("idkptDownloadNoise", NOISE_WHY, dev_DownloadNoise(m, slot, tiles, bytes, outSummary)); }
+int32_t idkptGetNoiseDevicePtr(idkpt_ctx* c, int32_t slot, void** outTiles, void** outSummary, size_t* outTileBytes) { ONE_ONLY("idkptGetNoiseDevicePtr", NOISE_WHY, dev_GetNoiseDevicePtr(m, slot, outTiles, outSummary, outTileBytes)); }
+int32_t idkptDownloadMoments(idkpt_ctx* c, int32_t slot, float* rgba, size_t bytes) { ONE_ONLY("idkptDownloadMoments", NOISE_WHY, dev_DownloadMoments(m, slot, rgba, bytes)); }
+int32_t idkptGetMomentsDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size_t* outBytes) { ONE_ONLY("idkptGetMomentsDevicePtr", NOISE_WHY, dev_GetMomentsDevicePtr(m, slot, outPtr, outBytes)); }
 
 int32_t idkptResetAccumulation(idkpt_ctx* c) { if (!c) return IDKPT_ERR_INVALID_ARGUMENT; for (dev_ctx* m : c->dev) dev_ResetAccumulation(m); return IDKPT_OK; }
 int32_t idkptSetSampleSequence(idkpt_ctx* c, uint32_t first, uint32_t stride) { REPLICATE(SetSampleSequence, first, stride); }
