@@ -138,6 +138,8 @@ struct DevOptions {
     int deferLast = 1;           // the last bounce's continuation (state, queue) on demand instead of every frame, where only radiance of it is visible (kernels_shade.hpp k_shade_last)
     int lastOcclusion = 1;       // ... and where only hit-or-miss of that bounce's traversal is read (no emission, no light hits: k_shade_last<false>), the launch stops every ray at its first
                                  // accepted triangle (k_trace2 OCCL); the closest hits are traced when the continuation is asked for (finish_deferred).  0: the closest-hit launch every frame
+    int foldLast = 1;            // ... and where that launch was the hit-or-miss one, the sky of its misses is added by k_final_draw instead of a k_shade_last pass of its own: the launch stores one byte per miss and
+                                 // no hit records (host_schedule.hpp want_fold).  0: k_shade_last<false> over the whole queue, as before
     int graphProbe = 0;          // developer build only: capture the next batch into a hipGraph and time this many replays (tools/graph_probe.py)
     int gridMidWaves = 20;       // launches below GRID_MID_RAYS rays: one-wave workgroups per CU (0: off) — see small_launch_grid
     int gridRaysX4 = 6;          // small launches: quarter-rays per lane the persistent grid is sized for (from the previous batch's counts; 0: gridHint's rule alone)
@@ -287,10 +289,12 @@ struct dev_ctx {
     bool sceneNested = false;       // every child box of every BLAS lies inside its parent's box (what k_trace2s's exactness argument needs; refits keep it)
     bool sceneNoEmission = false;   // no material / mesh of the uploaded scene emits and every texel is finite: a hit of the last bounce cannot change the radiance (k_shade_last)
     struct { bool valid = false, allHits = false; int j = 0, side = 0, B = 0; uint32_t total = 0, Npad = 0;
-             bool occl = false, pm = false; size_t ldsBytes = 0; uint32_t grid = 0; } defer;   // the last bounce of the last batch still owes its continuation (finish_deferred); occl: and its closest hits — the
-                                                                                             // launch was hit-or-miss (k_trace2 OCCL): pm = over the pixel-major list (hits per ray id), ldsBytes / grid = the plan's
+             bool occl = false, pm = false, fold = false; const uint32_t* list = nullptr; size_t ldsBytes = 0; uint32_t grid = 0; } defer;   // the last bounce of the last batch still owes its continuation (finish_deferred); occl: and its closest hits — the
+                                                                                             // launch was hit-or-miss (k_trace2 OCCL): pm = a PRIMARY launch over `list`, hits per ray id (the pixel-major list; folded: that list or the alive queue), ldsBytes / grid = the plan's;
+                                                                                             // fold: the bounce was folded into FinalDraw (k_restore_last restores the rays k_shade_last still owned)
     uint64_t occlLaunches = 0;   // traversal launches that were hit-or-miss (idkpt_stats.LastOcclusionLaunches), since idkptResetStats
-    DevBuf radSave, deferCount;
+    uint64_t foldBatches = 0;    // ... batches whose last bounce was folded into FinalDraw (idkpt_stats.LastFoldBatches)
+    DevBuf radSave, deferCount;  // deferCount: [0] the queue length of the deferred bounce, [1] TraceBufs::oddCount (reset with the batch counters)
     bool countersDirty = true;   // the batch counters were not reset by the last k_final_draw (first batch, or a batch that failed half way)
     uint32_t* hOverflow = nullptr; uint32_t* dOverflow = nullptr;   // host-mapped word the kernels set when a traversal-stack push is dropped (checked after every sync)
     int tlasNeed = 1;            // rows the TLAS walk needs (validated for host-built TLAS nodes; min(instances, TLAS_STACK_SIZE) for a device build)

@@ -31,6 +31,9 @@ static int alloc_frame_impl(dev_ctx* ctx)
     // Invariant between batches: NO byte has bit 0 ("continues") set.  k_shade_first / k_trace_fused set it, k_scan_local<true> of the same batch consumes and clears it.  That lets
     // a pixel-major batch leave the bytes of its sky-classified tiles unwritten: whatever they hold from an earlier batch (0, 2, 4) cannot enqueue a ray, and whether such a
     // pixel is "culled per tile" is read from the batch's tile classes, which take precedence over the byte (k_regen_culled).
+    // Stale CF_LAST_ENTERED / CF_LAST_MISSED (a folded last bounce, kernels_trace.hpp k_trace2 OCCL) are harmless for the same reason: a tile that is unclassified in a batch has every
+    // byte rewritten by that batch's k_gen_primary before anything sets or reads those bits, and a classified tile is answered from its class (k_final_draw never looks at its bytes).
+    HIPC(ctx->deferCount.ensure(64));                             // ([1]: TraceBufs::oddCount, counted from the first shading kernel of a batch on; zeroed by the first batch's counter reset)
     ctx->accum.assign(ctx->ringSize, 0u); ctx->curSlot = 0; ctx->ringStarted = false;
     ctx->products.release_all();                                   // they belong to a frame size and a ring: re-made (the moments images zeroed again) at their next use
     if (!owns_whole_frame(ctx)) ctx->noiseOn = 0;                  // a shard of the rows: the estimate needs the whole frame (host_noise.hpp)

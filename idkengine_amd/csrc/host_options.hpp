@@ -23,6 +23,7 @@ static int32_t dev_SetOption(dev_ctx* ctx, const char* name, int32_t value)
     else if (n == "grid_mid_waves") o.gridMidWaves = std::max(0, value);
     else if (n == "defer_last") o.deferLast = value != 0;
     else if (n == "last_occlusion") o.lastOcclusion = value != 0;
+    else if (n == "fold_last") o.foldLast = value != 0;
     else if (n == "split") { REQUIRE(value >= 0 && value <= 3, "idkptSetDeveloperOption: split is 0..3"); o.split = value; }
     else if (n == "split_donor") o.splitDonor = value != 0;
     else if (n == "split_peek") o.splitPeek = std::max(1, value);

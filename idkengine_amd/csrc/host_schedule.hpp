@@ -68,6 +68,13 @@ static bool want_occlusion(const dev_ctx* ctx, const TracePlan& plan, bool reads
     return readsOnlyHitOrMiss && ctx->opt.lastOcclusion != 0 && !plan.fused && (plan.walk == Walk::Plain || plan.walk == Walk::Fast) && !(split && plan.splitOk)
            && !plan.multiVer && !plan.counting && !ctx->counters && (ctx->opt.traceVariant == 0 || ctx->opt.traceVariant == 100);
 }
+// The folded last bounce (option fold_last) — the rule, whole: behind a hit-or-miss launch (tookOccl: want_occlusion above said yes) the only thing anybody reads of the bounce
+// before its continuation is asked for is "missed", and k_final_draw is the one reader of the sum that bit decides.  So the launch stores the bit per ray id (PRIMARY instantiation, over the
+// pixel-major list or the alive queue: trace_bounce) and no hit records, k_final_draw adds the sky of the misses, and k_shade_last<false> keeps the rays whose throughput is not finite.
+// Everything want_occlusion excludes keeps the k_shade_last pass.  (Measured on the default, interior and atrium views: profiles/last_fold.md — no view condition.)
+static bool want_fold(const dev_ctx* ctx, bool tookOccl) { return tookOccl && ctx->opt.foldLast != 0; }
+// ... and what the kernels that produce the rays of a last bounce are told before its launch is decided (Frame::markLast): whether it can still come out folded
+static bool may_fold(const dev_ctx* ctx, bool deferLast, bool deferAllHits) { return deferLast && !deferAllHits && ctx->opt.lastOcclusion != 0 && ctx->opt.foldLast != 0; }
 static uint32_t small_launch_grid(uint32_t fullGrid, uint32_t prev, int hintMul, int raysX4, uint32_t midGrid)
 {
     if (prev == 0u || hintMul <= 0) return fullGrid;
@@ -98,8 +105,8 @@ static void batch_views(dev_ctx* ctx, Batch& b, int B, uint32_t Npad)
 {
     b.ctx = ctx; b.st = ctx->stream; b.B = B; b.depth = ctx->st.RayDepth; b.N = (uint32_t)((size_t)ctx->W * ctx->rows); b.Npad = Npad; b.total = (uint32_t)B * Npad;
     b.gridTotal = (b.total + 255) / 256; b.scanBlocks = ((b.total + 63) / 64 + SCAN_WAVES_PER_BLOCK - 1) / SCAN_WAVES_PER_BLOCK;
-    b.rays = {ctx->rayO.as<float4>(), ctx->rayT.as<float4>(), ctx->rayR.as<float4>(), ctx->aovA.as<float4>(), ctx->aovN.as<float4>()}; b.hits = {ctx->hit.as<float4>(), ctx->hitCost.as<float>()};
-    b.tr = {ctx->trRec.as<float4>(), nullptr, nullptr}; b.trNone = {nullptr, nullptr, nullptr};
+    b.rays = {ctx->rayO.as<float4>(), ctx->rayT.as<float4>(), ctx->rayR.as<float4>(), ctx->aovA.as<float4>(), ctx->aovN.as<float4>(), ctx->contFlag.as<uint8_t>()}; b.hits = {ctx->hit.as<float4>(), ctx->hitCost.as<float>()};
+    b.tr = {ctx->trRec.as<float4>(), nullptr, nullptr, ctx->deferCount.as<uint32_t>() + 1}; b.trNone = {nullptr, nullptr, nullptr, nullptr};
     b.counts = ctx->counts.as<uint32_t>(); b.bases = ctx->bases.as<uint32_t>(); b.work = ctx->work.as<uint32_t>(); b.counters = ctx->counters64.as<uint64_t>(); b.hostCounts = ctx->dCountsMirror; b.hostBases = ctx->dBasesMirror;
     b.contMask = ctx->contMask.as<unsigned long long>(); b.waveLocal = ctx->waveCounts.as<uint32_t>(); b.blockSums = ctx->blockSums.as<uint32_t>(); b.keysTmp = ctx->keysTmp.as<uint32_t>();
     b.activeList = ctx->sortVals.as<uint32_t>(); b.activeCount = b.counts + (MAX_DEPTH_SLOTS - 1);
@@ -127,7 +134,7 @@ static int finish_deferred(dev_ctx* ctx)
     if (!ctx->defer.valid) return IDKPT_OK;
     ctx->defer.valid = false;
     Batch b; batch_views(ctx, b, ctx->defer.B, ctx->defer.Npad);
-    b.side = ctx->defer.side; b.f = ctx->lastFrame; b.s = make_dscene_last(ctx); b.multiVer = ctx->lastMulti;           // the scene states the deferred batch was traced with (its slots are pinned until now: ver_writable)
+    b.side = ctx->defer.side; b.f = ctx->lastFrame; b.f.markLast = 0; b.f.foldLast = 0; b.s = make_dscene_last(ctx); b.multiVer = ctx->lastMulti;           // the scene states the deferred batch was traced with (its slots are pinned until now: ver_writable)
     const uint32_t* q = ctx->queue[b.side].as<uint32_t>(); const uint32_t* cnt = ctx->deferCount.as<uint32_t>();               // (counts[j] itself was reset by the batch's last kernel)
     if (ctx->defer.occl) {
         // the bounce was traced hit-or-miss (k_trace2 OCCL): its closest hits first — the plain closest-hit kernel over the same list, the same records (trRec and the pixel-major list belong
@@ -139,11 +146,11 @@ static int finish_deferred(dev_ctx* ctx)
         // derived, and its hits are FAST's bit for bit (kernels_trace.hpp).  Every other field of the plan is off: no packets, nothing fused, one version, no counting, no split.
         TracePlan p{}; p.walk = Walk::Plain; p.ldsBytes = ctx->defer.ldsBytes; p.grid = ctx->defer.grid;
         Frame ft = b.f; if (ctx->defer.pm) ft.hitsByRid = 0;                  // (the PRIMARY instantiations read a list of ray ids and store per ray id: trace_bounce)
-        if (ctx->defer.pm) launch_trace2<true>(ctx, p, p.grid, b.st, b.s, ft, b.rays, b.tr, b.hits, ctx->pmList.as<uint32_t>(), cnt, b.work + j, b.counters, false, j);
+        if (ctx->defer.pm) launch_trace2<true>(ctx, p, p.grid, b.st, b.s, ft, b.rays, b.tr, b.hits, ctx->defer.list, cnt, b.work + j, b.counters, false, j);
         else launch_trace2<false>(ctx, p, p.grid, b.st, b.s, ft, b.rays, b.tr, b.hits, q, cnt, b.work + j, b.counters, false, j);
         ctx->defer.occl = false;
     }
-    with_flag(ctx->defer.allHits, [&](auto ALL) { launch(k_restore_last<ALL>, dim3(b.gridTotal), dim3(256), 0, b.st, b.rays, b.hits, q, cnt, ctx->radSave.as<float4>(), b.f.hitsByRid); });
+    with_flag(ctx->defer.allHits, [&](auto ALL) { launch(k_restore_last<ALL>, dim3(b.gridTotal), dim3(256), 0, b.st, b.rays, b.hits, q, cnt, ctx->radSave.as<float4>(), b.f.hitsByRid, ctx->defer.fold ? 1 : 0); });
     { int rc = bounce_tail(b, ctx->defer.j, q, cnt, nullptr, nullptr, false, b.tr); if (rc) return rc; }
     HIPC(hipGetLastError());
     ctx->lastQueueSide = 1 - b.side; ctx->countersDirty = true;                                          // (counts[j + 1] was written after the batch's reset: the next batch clears its counters itself)
@@ -218,7 +225,7 @@ static int frame_setup(Batch& b)
     graph_probe_begin(b);                                          // (developer build; from here on the batch may be captured instead of executed)
     if (ctx->timing) HIPC(hipEventRecord(ctx->evFrame[0], st));
     ctx->defer.valid = false;                                      // (a deferred last bounce of the previous batch that nobody asked for: its buffers are reused now)
-    if (ctx->countersDirty) { HIPC(hipMemsetAsync(b.work, 0, WORK_WORDS * 4, st)); HIPC(hipMemsetAsync(b.counts, 0, MAX_DEPTH_SLOTS * 4, st)); }   // (otherwise the previous batch's k_final_draw has reset them)
+    if (ctx->countersDirty) { HIPC(hipMemsetAsync(b.work, 0, WORK_WORDS * 4, st)); HIPC(hipMemsetAsync(b.counts, 0, MAX_DEPTH_SLOTS * 4, st)); HIPC(hipMemsetAsync(b.tr.oddCount, 0, 4, st)); }   // (otherwise the previous batch's k_final_draw has reset them)
     ctx->countersDirty = true;
     f.tlasCap = std::min(TLAS_STACK_SIZE, std::max(1, ctx->tlasNeed));
     f.grabUnitLog2 = std::min(24, std::max(6, ctx->opt.grabUnitLog2)); f.grabFixed = std::max(0, ctx->opt.grabFixed);   // work-list hand-out (kernels_trace.hpp)
@@ -372,6 +379,8 @@ static int sort_queue(Batch& b, uint32_t* q, uint32_t* k, const uint32_t* cnt)
 // The traversal launch of bounce j.  Its grid: the queue length is only known on the device; the length the same bounce had in the previous batch (pinned copy,
 // possibly one batch stale) is a good predictor, and a grid that is too small or too large only costs time (the waves are persistent)
 // readsOnlyHitOrMiss: nothing but hit-or-miss of this launch's records is read (flush_batch); returns whether the launch was the hit-or-miss one (want_occlusion)
+// ... and then, with fold_last, the folded one (want_fold): b.f.foldLast is set for it and for the kernels behind it, and the launch is a PRIMARY one — the miss bytes are per ray id, and
+// so are the hit records of the rays that keep their closest hit.  Over the alive queue where the bounce has no list of its own: a list of ray ids like any other (b.f.hitsByRid follows)
 static bool trace_bounce(Batch& b, int j, const uint32_t* q, const uint32_t* cnt, bool readsOnlyHitOrMiss)
 {
     dev_ctx* ctx = b.ctx; hipStream_t st = b.st; const int B = b.B;
@@ -380,10 +389,12 @@ static bool trace_bounce(Batch& b, int j, const uint32_t* q, const uint32_t* cnt
     uint32_t gridj = b.traceGrid;
     const bool split = want_split(ctx, prev, known, B), occl = b.fast && want_occlusion(ctx, b.plan, readsOnlyHitOrMiss, split);
     if (occl) ctx->occlLaunches++;
+    if (want_fold(ctx, occl)) { b.f.foldLast = 1; b.f.hitsByRid = 1; }
     if (ctx->opt.gridHint > 0 && ctx->lastBatch == B && ctx->hBases) gridj = small_launch_grid(b.traceGrid, ctx->hBases[(size_t)j * BS + B], ctx->opt.gridHint, ctx->opt.gridRaysX4, b.midGrid);
-    if (b.fast && b.pmBounce && j == 1) {   // the list k_shade_first wrote: ray ids, hits stored per ray id (the PRIMARY instantiations read exactly that)
+    if (b.fast && ((b.pmBounce && j == 1) || b.f.foldLast)) {   // the list k_shade_first wrote: ray ids, hits stored per ray id (the PRIMARY instantiations read exactly that); folded: or the alive queue
+        const bool pm = b.pmBounce && j == 1;
         Frame ft = b.f; ft.hitsByRid = 0;
-        launch_trace2<true>(ctx, b.plan, gridj, st, b.s, ft, b.rays, b.tr, b.hits, b.pmList, b.pmCount, b.work + j, b.counters, split, j, occl);
+        launch_trace2<true>(ctx, b.plan, gridj, st, b.s, ft, b.rays, b.tr, b.hits, pm ? b.pmList : q, pm ? b.pmCount : cnt, b.work + j, b.counters, split, j, occl);
     } else if (b.fast) launch_trace2<false>(ctx, b.plan, gridj, st, b.s, b.f, b.rays, b.tr, b.hits, q, cnt, b.work + j, b.counters, split, j, occl);
     else with_flag(ctx->counters, [&](auto COUNT) { launch(k_trace_queue<COUNT>, dim3(b.traceGrid), dim3(WAVE), b.plan.ldsBytes, st, b.s, b.f, b.rays, b.hits, q, cnt, b.work + j, b.counters); });
     TRACE_T1();
@@ -395,12 +406,16 @@ static bool trace_bounce(Batch& b, int j, const uint32_t* q, const uint32_t* cnt
 static int defer_last_bounce(Batch& b, int j, const uint32_t* q, const uint32_t* cnt, bool allHits, bool occl)
 {
     dev_ctx* ctx = b.ctx;
-    HIPC(ctx->radSave.ensure((size_t)ctx->maxBatch * ctx->Npad * 16)); HIPC(ctx->deferCount.ensure(64));
+    const bool fold = b.f.foldLast != 0, pm = b.pmBounce && j == 1;    // (fold: trace_bounce's decision, want_fold — the launch before this call was made for it)
+    HIPC(ctx->radSave.ensure((size_t)ctx->maxBatch * ctx->Npad * 16));
     auto shade_last = [&](auto ALL, auto VER) { launch(k_shade_last<ALL, VER>, dim3(b.gridTotal), dim3(256), 0, b.st, b.s, b.f, b.rays, b.hits, q, cnt, b.bases + j * BS, ctx->radSave.as<float4>(), ctx->deferCount.as<uint32_t>()); };
-    if (allHits) with_flag(b.multiVer, [&](auto VER) { shade_last(std::true_type{}, VER); });
+    // folded: the rays left to k_shade_last are the ones write_trace_ready counted (throughput not finite) — a small fixed grid that strides over the queue if there are any
+    if (fold) launch(k_shade_last_odd, dim3(std::min<uint32_t>(b.gridTotal, 256u)), dim3(256), 0, b.st, b.s, b.f, b.rays, b.hits, q, cnt, b.bases + j * BS, ctx->radSave.as<float4>(), ctx->deferCount.as<uint32_t>(), (const uint32_t*)b.tr.oddCount);
+    else if (allHits) with_flag(b.multiVer, [&](auto VER) { shade_last(std::true_type{}, VER); });
     else shade_last(std::false_type{}, std::false_type{});            // (misses only: the sky is not versioned)
+    if (fold) ctx->foldBatches++;
     ctx->defer.allHits = allHits; ctx->defer.valid = true; ctx->defer.j = j; ctx->defer.side = b.side; ctx->defer.B = b.B; ctx->defer.total = b.total; ctx->defer.Npad = b.Npad;
-    ctx->defer.occl = occl; ctx->defer.pm = b.pmBounce && j == 1; ctx->defer.ldsBytes = b.plan.ldsBytes; ctx->defer.grid = b.traceGrid;
+    ctx->defer.occl = occl; ctx->defer.fold = fold; ctx->defer.pm = pm || fold; ctx->defer.list = pm ? (const uint32_t*)b.pmList : q; ctx->defer.ldsBytes = b.plan.ldsBytes; ctx->defer.grid = b.traceGrid;
     return IDKPT_OK;
 }
 
@@ -410,10 +425,10 @@ static int final_draw(Batch& b)
     dev_ctx* ctx = b.ctx; hipStream_t st = b.st;
     ctx->lastQueueSide = b.side; ctx->lastQueueCountSlot = b.depth; ctx->lastFast = b.fast; ctx->lastNeedsRegen = b.fast; ctx->lastTileClass = b.tileClass != nullptr; ctx->lastBatch = b.B; ctx->lastFrame = b.f;
     if (ctx->noiseOn) {                                  // idkptSetNoiseEstimate: the sibling kernel folds the luminance moments in the same loop (one device, whole frame: host_noise.hpp)
-        launch(k_final_draw_noise, dim3((b.N + 255) / 256), dim3(256), 0, st, b.s, b.f, b.rays, image_ptr(ctx, 0, 0), image_ptr(ctx, 1, 0), image_ptr(ctx, 2, 0), b.N, b.tileClass, b.work, (uint32_t)WORK_WORDS, b.counts, (uint32_t)MAX_DEPTH_SLOTS,
+        launch(k_final_draw_noise, dim3((b.N + 255) / 256), dim3(256), 0, st, b.s, b.f, b.rays, image_ptr(ctx, 0, 0), image_ptr(ctx, 1, 0), image_ptr(ctx, 2, 0), b.N, b.tileClass, b.work, (uint32_t)WORK_WORDS, b.counts, (uint32_t)MAX_DEPTH_SLOTS, b.tr.oddCount,
                noise_moments_ptr(ctx, 0), noise_mom_stride(ctx));
     } else
-    launch(k_final_draw, dim3((b.N + 255) / 256), dim3(256), 0, st, b.s, b.f, b.rays, image_ptr(ctx, 0, 0), image_ptr(ctx, 1, 0), image_ptr(ctx, 2, 0), b.N, b.tileClass, b.work, (uint32_t)WORK_WORDS, b.counts, (uint32_t)MAX_DEPTH_SLOTS);
+    launch(k_final_draw, dim3((b.N + 255) / 256), dim3(256), 0, st, b.s, b.f, b.rays, image_ptr(ctx, 0, 0), image_ptr(ctx, 1, 0), image_ptr(ctx, 2, 0), b.N, b.tileClass, b.work, (uint32_t)WORK_WORDS, b.counts, (uint32_t)MAX_DEPTH_SLOTS, b.tr.oddCount);
     HIPC(hipGetLastError()); ctx->countersDirty = false;
     graph_probe_end(b);
     // queue lengths stay on the GPU during the batch; k_scan_blocks mirrors them into host-mapped memory for GetStats and the queue downloads (no copy, no sync here)
@@ -435,10 +450,12 @@ static int flush_batch(dev_ctx* ctx)
     Batch b; batch_views(ctx, b, (int)ctx->pending.size(), ctx->Npad); int rc;
     if ((rc = stage_versions_cameras(b))) return rc;
     if ((rc = frame_setup(b))) return rc;
-    if ((rc = b.fast ? first_hit_fast(b) : first_hit_generic(b))) return rc;
     // may the last bounce's continuation wait until somebody asks for it?  (k_shade_last: only where a hit of that bounce cannot change the radiance and nothing else of it reaches the frame)
     const bool deferLast = b.fast && b.depth >= 2 && ctx->opt.deferLast != 0 && !b.f.outputAovs && !b.debug;
     const bool deferAllHits = !(ctx->sceneNoEmission && !(b.f.g.DoTraceLights && b.s.lightCount > 0));   // a hit of the last bounce may add radiance: emission somewhere in the scene, or light hits
+    const bool mayFold = may_fold(ctx, deferLast, deferAllHits);
+    b.f.markLast = (mayFold && b.depth == 2) ? 1 : 0;                     // (what FirstHit's shading lets continue enters bounce 1)
+    if ((rc = b.fast ? first_hit_fast(b) : first_hit_generic(b))) return rc;
     for (int j = 1; j < b.depth; j++) {
         uint32_t* q = ctx->queue[b.side].as<uint32_t>(); uint32_t* k = ctx->keys[b.side].as<uint32_t>();
         const uint32_t* cnt = b.counts + j; const uint32_t* gbase;
@@ -450,6 +467,7 @@ static int flush_batch(dev_ctx* ctx)
         bool tookOccl = false;
         if (!b.plan.fused) tookOccl = trace_bounce(b, j, q, cnt, deferThis && !deferAllHits);
         if (deferThis) { if ((rc = defer_last_bounce(b, j, q, cnt, deferAllHits, tookOccl))) return rc; break; }
+        b.f.markLast = (mayFold && j + 1 == b.depth - 1) ? 1 : 0;         // (this tail's continuing rays enter bounce j + 1)
         if ((rc = bounce_tail(b, j, q, cnt, gbase, (unsigned long long*)(j + 1 < b.depth ? b.counters + 2 : nullptr), ctx->evBounce != nullptr, b.fast ? b.tr : b.trNone))) return rc;
         b.side = 1 - b.side;
     }

@@ -47,7 +47,19 @@ __device__ __forceinline__ void final_draw_body(const DScene& s, const Frame& f,
         // pixels of a pre-classified tile (k_classify_tiles): the radiance is the known sky colour of the class; nothing was stored per sample
         const uint32_t cls = !tileClass ? 0u : (f.tilePerSample ? tileClass[(size_t)k * nTilesAll + tile] : sharedCls);   // one class per camera / scene version
         f3 nr = splat3(0.0f);
-        if (cls == 0u) { float4 c = rays.rad_py[rid]; nr = mk3(c.x, c.y, c.z); }
+        if (cls == 0u) {
+            const float4 c = rays.rad_py[rid]; nr = mk3(c.x, c.y, c.z);
+            // folded last bounce (Frame::foldLast): a ray that missed there still owes the sky — k_shade_last's miss branch, its operations in its order, on the operands it would
+            // have gathered; rad_py keeps the value every other reader expects (finish_deferred).  A throughput that is not finite is k_shade_last's own (it did write rad_py).
+            // (the byte is this batch's: k_gen_primary rewrote every byte of an unclassified tile)
+            if (f.foldLast && (rays.flag[rid] & CF_LAST_MISSED)) {
+                const float4 b = rays.thr_px[rid];
+                if (__builtin_isfinite(b.x) && __builtin_isfinite(b.y) && __builtin_isfinite(b.z)) {
+                    const f3 albedo = SampleSky(s, DecodeUnitVec(b.w, c.w));
+                    nr = mk3(c.x, c.y, c.z) + albedo * mk3(b.x, b.y, b.z);
+                }
+            }
+        }
         else if (cls <= 6u) { const float4 p = s.sky[cls - 1u]; nr = splat3(0.0f) + mk3(p.x, p.y, p.z) * splat3(1.0f); }
         else if (cls == 8u) {                            // textured sky: the miss branch of FirstHit (FirstHit:225-233) for this sample's ray, generated here (k_regen_culled does the same on demand)
             f3 origin; f2 pd; uint32_t seed;
@@ -65,20 +77,20 @@ __device__ __forceinline__ void final_draw_body(const DScene& s, const Frame& f,
     if constexpr (NOISE) imgMoments[(size_t)slot * momStride + i] = make_float4(m1, m2, 0.0f, 1.0f);
 }
 __global__ __launch_bounds__(256) void k_final_draw(DScene s, Frame f, RayBufs rays, float4* imgResult, float4* imgAlbedo, float4* imgNormal, uint32_t N, const uint8_t* tileClass,
-                                                    uint32_t* zeroWork, uint32_t nWork, uint32_t* zeroCounts, uint32_t nCounts)
+                                                    uint32_t* zeroWork, uint32_t nWork, uint32_t* zeroCounts, uint32_t nCounts, uint32_t* zeroOdd /* TraceBufs::oddCount */)
 {
     // last kernel of a batch: nothing reads this batch's work-list and queue-length counters any more, so they are reset here for the next batch
     // (two memset launches per batch less: they were 5 % of a frame that is rendered alone)
-    if (blockIdx.x == 0) { for (uint32_t k = threadIdx.x; k < nWork; k += blockDim.x) zeroWork[k] = 0u; for (uint32_t k = threadIdx.x; k < nCounts; k += blockDim.x) zeroCounts[k] = 0u; }
+    if (blockIdx.x == 0) { for (uint32_t k = threadIdx.x; k < nWork; k += blockDim.x) zeroWork[k] = 0u; for (uint32_t k = threadIdx.x; k < nCounts; k += blockDim.x) zeroCounts[k] = 0u; if (threadIdx.x == 0) *zeroOdd = 0u; }
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
     final_draw_body<false>(s, f, rays, imgResult, imgAlbedo, imgNormal, N, tileClass, i, nullptr, 0);
 }
 // the same with the moments image (the switch of idkptSetNoiseEstimate is on): 32 B more per pixel read and written
 __global__ __launch_bounds__(256) void k_final_draw_noise(DScene s, Frame f, RayBufs rays, float4* imgResult, float4* imgAlbedo, float4* imgNormal, uint32_t N, const uint8_t* tileClass,
-                                                          uint32_t* zeroWork, uint32_t nWork, uint32_t* zeroCounts, uint32_t nCounts, float4* imgMoments, size_t momStride)
+                                                          uint32_t* zeroWork, uint32_t nWork, uint32_t* zeroCounts, uint32_t nCounts, uint32_t* zeroOdd, float4* imgMoments, size_t momStride)
 {
-    if (blockIdx.x == 0) { for (uint32_t k = threadIdx.x; k < nWork; k += blockDim.x) zeroWork[k] = 0u; for (uint32_t k = threadIdx.x; k < nCounts; k += blockDim.x) zeroCounts[k] = 0u; }   // (as k_final_draw)
+    if (blockIdx.x == 0) { for (uint32_t k = threadIdx.x; k < nWork; k += blockDim.x) zeroWork[k] = 0u; for (uint32_t k = threadIdx.x; k < nCounts; k += blockDim.x) zeroCounts[k] = 0u; if (threadIdx.x == 0) *zeroOdd = 0u; }   // (as k_final_draw)
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
     final_draw_body<true>(s, f, rays, imgResult, imgAlbedo, imgNormal, N, tileClass, i, imgMoments, momStride);
@@ -95,14 +107,15 @@ __global__ __launch_bounds__(256) void k_regen_culled(DScene s, Frame f, RayBufs
     uint8_t flag = contFlag[rid];
     if (tileClass) {
         const uint32_t px = pix % (uint32_t)f.W, py = pix / (uint32_t)f.W, tilesX = ((uint32_t)f.W + 7) / 8, nTilesAll = tilesX * (((uint32_t)f.rows + 7) / 8);
-        if (tileClass[(f.tilePerSample ? (size_t)smp * nTilesAll : 0) + (py >> 3) * tilesX + (px >> 3)] != 0u) flag = 4;
+        if (tileClass[(f.tilePerSample ? (size_t)smp * nTilesAll : 0) + (py >> 3) * tilesX + (px >> 3)] != 0u) flag = CF_CULLED_TILE;
     }
-    if (flag != 2 && flag != 4) return;                                 // 2: culled per pixel, 4: culled per tile (no ray was generated at all); bit 0 = continues
+    flag &= (uint8_t)(CF_CULLED_PIXEL | CF_CULLED_TILE);                // (a ray that was generated may carry CF_LAST_* by now; k_gen_primary writes one of the two, or neither)
+    if (flag == 0) return;                                              // culled per pixel, or per tile (no ray was generated at all)
     f3 origin; f2 pd; uint32_t seed;
     gen_primary(f, smp, pix, sample_index(f, smp), origin, pd, seed);
     rays.o_ior[rid] = make_float4(origin.x, origin.y, origin.z, 1.0f);
     rays.thr_px[rid] = make_float4(1.0f, 1.0f, 1.0f, pd.x);
-    if (flag == 4) {                                                    // the miss branch of FirstHit (FirstHit:225-233) for a pixel nothing was stored for
+    if (flag == CF_CULLED_TILE) {                                       // the miss branch of FirstHit (FirstHit:225-233) for a pixel nothing was stored for
         const f3 albedo = SampleSky(s, DecodeUnitVec(pd.x, pd.y));
         const f3 radiance = splat3(0.0f) + albedo * splat3(1.0f);
         rays.rad_py[rid] = make_float4(radiance.x, radiance.y, radiance.z, pd.y);

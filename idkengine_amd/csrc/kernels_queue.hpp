@@ -52,7 +52,7 @@ __global__ __launch_bounds__(SCAN_WAVES_PER_BLOCK) void k_scan_local(const uint3
         if (FROM_FLAGS) {
             // The "continues" bits (bit 0 of a ray's byte, set by k_shade_first / k_trace_fused) are consumed here and cleared again: between batches no byte has bit 0 set,
             // so a slot this batch does not write at all (a tile classified as sky, kernels_trace.hpp k_gen_primary) cannot enqueue a ray that continued in an earlier batch.
-            // Bits 1 and 2 (culled per pixel / per tile) stay for k_regen_culled.
+            // Bits 1 and 2 (culled per pixel / per tile) stay for k_regen_culled, bits 3 and 4 (CF_LAST_*: set after this kernel, in the same batch) for k_final_draw.
             uint4* p = reinterpret_cast<uint4*>(contFlag + (size_t)w * 64);
             m = 0ull;
             for (int q = 0; q < 4; q++) {

@@ -26,6 +26,7 @@ DEV void write_trace_ready(const DScene& s, const Frame& f, const TraceBufs& tr,
     // ld.w = 1 marks a ray whose throughput is not finite: should the launch that traces it be the hit-or-miss one (k_trace2 OCCL: the deferred last bounce), this ray still gets its
     // closest hit — k_shade_last runs ShadeHit on it (0 * inf is not 0).  The throughput stored with the ray state is this one; no other kernel looks at the word outside query mode.
     const float wantClosest = (__builtin_isfinite(r.throughput.x) && __builtin_isfinite(r.throughput.y) && __builtin_isfinite(r.throughput.z)) ? 0.0f : 1.0f;
+    if (wantClosest != 0.0f && tr.oddCount) atomicAdd(tr.oddCount, 1u);   // (almost never: the folded k_shade_last<false> returns at once while the batch has marked nothing)
     tr.rec[4 * (size_t)rid] = make_float4(lo.x, lo.y, lo.z, rootT); tr.rec[4 * (size_t)rid + 1] = make_float4(ld.x, ld.y, ld.z, wantClosest);
     tr.rec[4 * (size_t)rid + 2] = make_float4(iv.x, iv.y, iv.z, 0.0f);
 }
@@ -69,7 +70,7 @@ __global__ __launch_bounds__(256) void k_shade_first(DScene s0, Frame f, RayBufs
         rays.rad_py[rid] = make_float4(r.radiance.x, r.radiance.y, r.radiance.z, r.pdy);
         if (f.outputAovs) { rays.aovA[rid] = make_float4(aov.albedo.x, aov.albedo.y, aov.albedo.z, aov.newWeight); rays.aovN[rid] = make_float4(aov.normal.x, aov.normal.y, aov.normal.z, 0.0f); }
         seedsAndKeys[rid] = (key & ((1u << IDKPT_SORT_KEY_BITS) - 1u)) | (smp << IDKPT_SORT_KEY_BITS);
-        if (cont) { contFlag[rid] = 1; write_trace_ready(s, f, tr, rid, r); }
+        if (cont) { contFlag[rid] = (uint8_t)(CF_CONTINUES | (f.markLast ? CF_LAST_ENTERED : 0)); write_trace_ready(s, f, tr, rid, r); }
     }
     if (pmList) {
         // the first bounce's work list in THIS kernel's order — the pixel-major order of the primary list (k_gen_primary): the continuing rays of a pixel's samples side by side,
@@ -132,6 +133,7 @@ __global__ __launch_bounds__(256) void k_shade(DScene s0, Frame f, RayBufs rays,
             rays.rad_py[idx] = make_float4(r.radiance.x, r.radiance.y, r.radiance.z, r.pdy);
             if (f.outputAovs) { rays.aovA[idx] = make_float4(aov.albedo.x, aov.albedo.y, aov.albedo.z, aov.newWeight); rays.aovN[idx] = make_float4(aov.normal.x, aov.normal.y, aov.normal.z, 0.0f); }
             if (cont && tr.rec) write_trace_ready(s, f, tr, idx, r);
+            if (!FIRST && cont && f.markLast) rays.flag[idx] = CF_LAST_ENTERED;   // (bit 0 stays clear: this bounce's queue is built from the ballots below, not from the bytes)
         }
         // NHit:81 masks the key to 21 bits; the sample index goes above it so that the batch-wide sort stays grouped by sample
         keysTmp[slot] = (key & ((1u << IDKPT_SORT_KEY_BITS) - 1u)) | (smp << IDKPT_SORT_KEY_BITS);
@@ -150,19 +152,16 @@ __global__ __launch_bounds__(256) void k_shade(DScene s0, Frame f, RayBufs rays,
 // else of the bounce — ray state, alive queue, counts: what idkptDownloadRays / idkptDownloadAliveQueue / the next scene update may look at — is produced on demand
 // by the ordinary kernels (finish_deferred in idkpt.hip: k_restore_last, then k_shade<false>, the scan and the scatter), bit for bit what the eager path
 // leaves.  A hit whose throughput is not finite (0 * inf is not 0) takes ShadeHit on a copy of its state right here.
-template <bool ALL_HITS /* the scene emits, or lights are hit: every hit may add radiance */, bool VER = false>
-__global__ __launch_bounds__(256) void k_shade_last(DScene s0, Frame f, RayBufs rays, HitBufs hits, const uint32_t* queue, const uint32_t* countPtr, const uint32_t* qbase,
-                                                    float4* radSave, uint32_t* deferCount)
+// One slot of the queue entering the last bounce.  ODD_ONLY (a folded batch, below): only the rays whose throughput is not finite — of the others the launch stored no hit record.
+template <bool ALL_HITS /* the scene emits, or lights are hit: every hit may add radiance */, bool VER, bool ODD_ONLY>
+__device__ __forceinline__ void shade_last_slot(const DScene& s0, const Frame& f, const RayBufs& rays, const HitBufs& hits, const uint32_t* queue, const uint32_t* qbase, float4* radSave, uint32_t slot)
 {
-    const uint32_t N = *countPtr;
-    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
-    if (slot == 0u) *deferCount = N;                                // (the batch's last kernel resets the queue lengths: the on-demand pass reads this copy)
-    if (slot >= N) return;
     const uint32_t idx = queue[slot];
-    const HitRec hit = load_hit(hits, f.hitsByRid ? idx : slot);
     const float4 b = rays.thr_px[idx];
-    const bool miss = hit.T == PT_FLOAT_MAX;
     const bool odd = ALL_HITS || !(__builtin_isfinite(b.x) && __builtin_isfinite(b.y) && __builtin_isfinite(b.z));
+    if (ODD_ONLY && !odd) return;
+    const HitRec hit = load_hit(hits, f.hitsByRid ? idx : slot);
+    const bool miss = hit.T == PT_FLOAT_MAX;
     if (!miss && !odd) return;
     const float4 c = rays.rad_py[idx];
     radSave[slot] = c;
@@ -183,15 +182,39 @@ __global__ __launch_bounds__(256) void k_shade_last(DScene s0, Frame f, RayBufs 
         rays.rad_py[idx] = make_float4(r.radiance.x, r.radiance.y, r.radiance.z, c.w);
     }
 }
+template <bool ALL_HITS, bool VER = false>
+__global__ __launch_bounds__(256) void k_shade_last(DScene s0, Frame f, RayBufs rays, HitBufs hits, const uint32_t* queue, const uint32_t* countPtr, const uint32_t* qbase,
+                                                    float4* radSave, uint32_t* deferCount)
+{
+    const uint32_t N = *countPtr;
+    const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+    if (slot == 0u) *deferCount = N;                                // (the batch's last kernel resets the queue lengths: the on-demand pass reads this copy)
+    if (slot >= N) return;
+    shade_last_slot<ALL_HITS, VER, false>(s0, f, rays, hits, queue, qbase, radSave, slot);
+}
+// The same behind a FOLDED last bounce (Frame::foldLast; misses only, one scene version): k_final_draw adds the sky of the misses itself, so what is left to this kernel are the rays
+// whose throughput is not finite — they walked closest-hit and have their hit record, per ray id.  write_trace_ready counted the rays it marked (*oddCount: that many or more,
+// earlier bounces' included): almost always none — a small fixed grid reads one word and is done; otherwise it strides over the queue.
+__global__ __launch_bounds__(256) void k_shade_last_odd(DScene s0, Frame f, RayBufs rays, HitBufs hits, const uint32_t* queue, const uint32_t* countPtr, const uint32_t* qbase,
+                                                        float4* radSave, uint32_t* deferCount, const uint32_t* oddCount)
+{
+    const uint32_t N = *countPtr;
+    const uint32_t first = blockIdx.x * blockDim.x + threadIdx.x;
+    if (first == 0u) *deferCount = N;
+    if (*oddCount == 0u) return;
+    for (unsigned long long slot = first; slot < N; slot += (unsigned long long)gridDim.x * blockDim.x) shade_last_slot<false, false, true>(s0, f, rays, hits, queue, qbase, radSave, (uint32_t)slot);
+}
 // on demand, before the ordinary kernels run for the deferred bounce: the radiance k_shade_last replaced
+// folded: k_shade_last touched only the rays whose throughput is not finite (radSave holds nothing for a miss k_final_draw added the sky of: its rad_py never changed)
 template <bool ALL_HITS>
-__global__ __launch_bounds__(256) void k_restore_last(RayBufs rays, HitBufs hits, const uint32_t* queue, const uint32_t* countPtr, const float4* radSave, int hitsByRid)
+__global__ __launch_bounds__(256) void k_restore_last(RayBufs rays, HitBufs hits, const uint32_t* queue, const uint32_t* countPtr, const float4* radSave, int hitsByRid, int folded)
 {
     const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
     if (slot >= *countPtr) return;
     const uint32_t idx = queue[slot];
-    const HitRec hit = load_hit(hits, hitsByRid ? idx : slot);
     const float4 b = rays.thr_px[idx];
-    if (ALL_HITS || hit.T == PT_FLOAT_MAX || !(__builtin_isfinite(b.x) && __builtin_isfinite(b.y) && __builtin_isfinite(b.z))) rays.rad_py[idx] = radSave[slot];
+    bool restore = ALL_HITS || !(__builtin_isfinite(b.x) && __builtin_isfinite(b.y) && __builtin_isfinite(b.z));
+    if (!restore && !folded) restore = load_hit(hits, hitsByRid ? idx : slot).T == PT_FLOAT_MAX;
+    if (restore) rays.rad_py[idx] = radSave[slot];
 }
 

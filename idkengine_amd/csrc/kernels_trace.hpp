@@ -202,7 +202,7 @@ __global__ __launch_bounds__(1024) void k_gen_primary(DScene s0, Frame f, RayBuf
     if (valid && cls != 0u) {
         // the whole tile is a proven miss with a known sky colour (k_classify_tiles): FirstHit's miss branch without generating the ray
         // k_final_draw takes the colour from the tile class, idkptDownloadRays regenerates the ray state: one flag byte is all that is stored
-        contFlag[rid] = 4;                                               // (bit 0 = "continues" must stay clear) origin / direction planes regenerated on demand (k_regen_culled)
+        contFlag[rid] = CF_CULLED_TILE;                                  // (bit 0 = "continues" must stay clear) origin / direction planes regenerated on demand (k_regen_culled)
     } else if (valid) {
         f3 origin; f2 pd; uint32_t seed;
         gen_primary(f, smp, pix, sample_index(f, smp), origin, pd, seed);
@@ -257,7 +257,7 @@ __global__ __launch_bounds__(1024) void k_gen_primary(DScene s0, Frame f, RayBuf
         // written; the flag lets idkptDownloadRays regenerate them on demand (k_regen_culled).
         // A surviving ray's planes are a function of (pixel, sample): in lean mode (52 of its 105 B) k_shade_first recomputes them.
         if (keep && !lean) { rays.o_ior[rid] = make_float4(origin.x, origin.y, origin.z, 1.0f); rays.thr_px[rid] = make_float4(1.0f, 1.0f, 1.0f, pd.x); }
-        contFlag[rid] = keep ? 0 : 2;       // also resets the continue flag of this ray id (k_shade_first sets 1); pad ids stay 0 from allocation
+        contFlag[rid] = keep ? 0 : CF_CULLED_PIXEL;   // also resets every other bit of this ray id (k_shade_first sets CF_CONTINUES, a folded last bounce CF_LAST_*); pad ids stay 0 from allocation
         if (!(keep && lean)) rays.rad_py[rid] = make_float4(radiance.x, radiance.y, radiance.z, pd.y);
     }
     // append the survivors: one atomic per 16-wave workgroup (a single counter word saturates at ~88 atomics/us; one atomic per 32 / 64 / 128 waves was
@@ -314,6 +314,7 @@ __global__ __launch_bounds__(1024) void k_gen_primary(DScene s0, Frame f, RayBuf
 // only reader (k_shade_last<false>) asks `T == PT_FLOAT_MAX` and nothing else.  The node step is the closest-hit one (nearer child first); the first triangle accepted by `t < T` ends the
 // lane: its stack, its parked leaf's remaining triangles are dropped.  Hit-or-miss is what the closest-hit walk reports, ray for ray; T of a hit is SOME accepted triangle's,
 // triangle id and barycentrics with it.  A ray whose producer marked it (record[1].w != 0: its throughput is not finite, k_shade_last runs ShadeHit on its real hit) walks closest-hit.
+// Under Frame::foldLast the reader of that bit is k_final_draw: an unmarked lane stores CF_LAST_MISSED into its ray's byte on a miss and no hit record either way (the retire step below).
 template <bool PRIMARY, bool COUNT, int REFILL_MIN = 32, int OCC = 1, bool PROF = false, int LEAF_MIN = 24, int MODE = 0, int DBG = 0, bool VER = false, bool ANY = false, bool FAST = false, bool OCCL = false>
 __global__ __launch_bounds__(WAVE, OCC) void k_trace2(DScene s, Frame f, RayBufs rays, TraceBufs tr, HitBufs hits, const uint32_t* list, const uint32_t* countPtr, uint32_t* workCounter, uint64_t* counters)
 {
@@ -646,7 +647,10 @@ __global__ __launch_bounds__(WAVE, OCC) void k_trace2(DScene s, Frame f, RayBufs
         PROF_MARK(2);
         // ---- retire finished rays (MULTI: only after the last instance)
         if (active && top == 0u && (!MULTI || (TLAS ? !moreInst : instIdx >= (uint32_t)s.instanceCount))) {
-            store_hit(hits, slot, hitT, hbx, hby, hitTri, hitXform);
+            // folded last bounce (Frame::foldLast; the host launches it PRIMARY: slot = ray id): hit-or-miss is one bit, and k_final_draw is its reader — a miss stores its byte
+            // (a plain store: k_scan_local<true> cleared bit 0 long ago, and no other bit is set in the byte of a ray that got this far), a hit stores nothing at all
+            if (OCCL && occl && f.foldLast) { if (hitT == PT_FLOAT_MAX) rays.flag[slot] = (uint8_t)(CF_LAST_ENTERED | CF_LAST_MISSED); }
+            else store_hit(hits, slot, hitT, hbx, hby, hitTri, hitXform);
             active = false;
         }
     }

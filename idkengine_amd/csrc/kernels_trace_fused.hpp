@@ -174,7 +174,7 @@ __global__ __launch_bounds__(WAVE, 1) void k_trace_fused(DScene s, Frame f, RayB
             if (f.outputAovs) { rays.aovA[rid] = make_float4(aov.albedo.x, aov.albedo.y, aov.albedo.z, aov.newWeight); rays.aovN[rid] = make_float4(aov.normal.x, aov.normal.y, aov.normal.z, 0.0f); }
             seedsAndKeys[rid] = (key & ((1u << IDKPT_SORT_KEY_BITS) - 1u)) | (smp << IDKPT_SORT_KEY_BITS);
             if (cont) {
-                contFlag[rid] = 1;
+                contFlag[rid] = CF_CONTINUES;                        // (the fused launch is never the hit-or-miss one: nothing of it is folded into FinalDraw)
                 // the bounce ray, prepared as write_trace_ready does (NHit:93, BVHIntersect.glsl:281-282, IntersectionRoutines.glsl:29) — into registers instead of the record
                 const f3 wd = DecodeUnitVec(r.pdx, r.pdy);
                 const M34 inv = load_inv_model(s, inst.MeshTransformId);

@@ -81,6 +81,16 @@ struct Frame {
     int instTlas;               // several instances without USE_TLAS walked through the library's own TLAS (kernels_trace_inst.hpp): the producers of a ray also write its world 1/dir
     int packet;                 // this batch's primary launch is a packet launch (kernels_packet.hpp; decided by the host per batch: host_launch.hpp packet_decide)
     int tilePerSample;          // k_classify_tiles ran once per sample of the batch (per-sample cameras or scene versions): tile classes are indexed [sample][tile]
+    int markLast;               // the rays this kernel lets continue enter a last bounce that may be folded into FinalDraw: their byte gets CF_LAST_ENTERED (k_shade_first, k_shade<false>; host_schedule.hpp may_fold)
+    int foldLast;               // the last bounce of this batch is folded (host_schedule.hpp want_fold): its hit-or-miss launch stores CF_LAST_MISSED instead of hit records, k_final_draw adds the sky of those rays
+};
+// RayBufs::flag (dev_ctx::contFlag), one byte per ray id.  Bit 0 lives from k_shade_first / k_trace_fused to k_scan_local<true> of the same batch; the others until the slot is next written.
+enum : uint8_t {
+    CF_CONTINUES = 1,           // the primary ray continues into bounce 1 (consumed and cleared by k_scan_local<true>)
+    CF_CULLED_PIXEL = 2,        // the primary ray missed the root box: no state planes stored (k_regen_culled)
+    CF_CULLED_TILE = 4,         // ... its whole tile did (k_classify_tiles): nothing stored at all
+    CF_LAST_ENTERED = 8,        // the ray entered a last bounce that may be folded (Frame::markLast)
+    CF_LAST_MISSED = 16,        // ... and missed: stored, together with CF_LAST_ENTERED, by the hit-or-miss walk of a folded batch (k_trace2 OCCL), read by k_final_draw
 };
 #define MAX_BATCH 256
 
@@ -90,6 +100,7 @@ struct RayBufs {                // SoA planes of the reference's GpuWavefrontRay
     float4* rad_py;             // Radiance.xyz, PackedDirectionY
     float4* aovA;               // Albedo.xyz, NewWeight
     float4* aovN;               // Normal.xyz, pad
+    uint8_t* flag;              // the CF_* byte of every ray id
 };
 struct TraceBufs {              // derived, per ray id: the ray ready for the traversal kernel, one 64-B record (the size and alignment of a node pair, so
     float4* rec;                // that a refill touches one cache line per ray instead of three): [0] RayTransform(origin) (Ray.glsl:7-12), .w = tMin of
@@ -98,6 +109,7 @@ struct TraceBufs {              // derived, per ray id: the ray ready for the tr
     // a bounce launch over a SUBSET of the queue (null: the whole queue in order): the launch hands out positions of `order`; order[i] = queue slot, orderIdx[i] = the ray id
     // in that slot — the exact re-trace behind a wide-node launch (kernels_wide.hpp).  The slot a hit is stored at — which seeds NHit's RNG (NHit/compute.glsl:54) — stays what it is.
     const uint32_t* order; const uint32_t* orderIdx;
+    uint32_t* oddCount;         // (or null) write_trace_ready counts the rays it marks "throughput not finite" here: the folded k_shade_last<false> has nothing to do while it is 0
 };
 struct HitBufs {                // indexed by queue slot: one 32-B record per slot (one aligned store sector instead of a 16-B and a 4-B partial write)
     float4* hit;                // [2*slot] = T, BaryXY.x, BaryXY.y, TriangleId (bits); [2*slot+1].x = MeshTransformId or light index (bits)

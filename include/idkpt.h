@@ -234,6 +234,7 @@ typedef struct idkpt_stats {
     /* the deferred last bounce traced hit-or-miss (developer option "last_occlusion", csrc/kernels_trace.hpp k_trace2 OCCL).  Added at ABI 12 without a new number: see below */
     uint64_t LastOcclusionLaunches; /* traversal launches that stopped every ray at its first accepted triangle, since idkptResetStats (the closest-hit launch that idkptDownloadRays & co. ask for
                                      * afterwards is neither counted here nor in TraceLaunches / RaysTraced) */
+    uint64_t LastFoldBatches;       /* ... batches of them whose misses got their sky in FinalDraw instead of a pass of its own (developer option "fold_last"), since idkptResetStats.  Added like the field above */
 } idkpt_stats;
 /* The layout above only ever GROWS at its end.  IDKPT_ABI_VERSION counted its growths up to ABI 3; since idkptGetStatsSized exists a growth of this struct no longer takes a number
  * (LastOcclusionLaunches came at 12 without one): the size a host passes IS its version of the struct, and a host that was not built from this tree must use idkptGetStatsSized —
@@ -838,6 +839,8 @@ IDKPT_API int32_t idkptEnableTiming(idkpt_ctx* ctx, int32_t enable);
  *                                    first triangle it meets (k_trace2 OCCL, csrc/kernels_trace.hpp; rays whose throughput is not finite keep their closest hit).  One BLAS instance, one scene version in the
  *                                    batch, counters off, a launch that is not split, no multi-GPU bounce exchange; otherwise, and with 0, the closest-hit launch.  The closest hits are traced when the
  *                                    continuation is asked for.  Frames, ray state, queues and counts are bit-identical either way; idkpt_stats.LastOcclusionLaunches counts the launches
+ *     "fold_last"        0 / 1*      ... and behind such a launch FinalDraw adds the sky of the misses itself: the launch stores one byte per miss instead of a hit record per ray, and the pass that
+ *                                    read those records (k_shade_last) is left with the rays whose throughput is not finite.  Bit-identical either way; idkpt_stats.LastFoldBatches counts the batches
  *     "gen_pixel_major"  >= 0 (8*)   batches of at least this many samples hand their primary rays to the traversal pixel by pixel (a wave = 4 pixels x 16 samples instead of an 8x8 tile of one
  *                                    sample; profiles/r05_pixel_major.md); 0 = never.   "gen_group_max" 1-16 (16*): samples per group of that list
  *     "bounce_pixel_major" 0-2 (1*) the first bounce traced in that order too (its own work list, hits per ray id): 0 never, 1 on sparse views, 2 always

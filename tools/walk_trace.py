@@ -32,6 +32,7 @@ SITUATIONS = [
     ("one_blas_wide", "one_blas", dict(packet=0, wide=1), {}, "packet = 0"),
     ("one_blas_wide_packet_forced", "one_blas", dict(packet=2, wide=1, wide_count=1), {}, "packet = 2"),
     ("one_blas_no_last_occlusion", "one_blas", dict(packet=0, last_occlusion=0), {}, "packet = 0"),
+    ("one_blas_no_fold_last", "one_blas", dict(packet=0, fold_last=0), {}, "packet = 0"),
     ("one_blas_no_pair_nodes_no_split", "one_blas", dict(packet=0, pair_nodes=0, split=0), {}, "packet = 0"),
     ("one_blas_fused", "one_blas", dict(packet=0, fused=2), {}, "packet = 0"),
     ("one_blas_split_forced", "one_blas", dict(packet=0, split=2), {}, "packet = 0"),
