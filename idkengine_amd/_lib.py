@@ -20,7 +20,7 @@ SYMBOLS = [
     "idkptBloom", "idkptGetBloomInfo", "idkptDownloadBloom", "idkptGetBloomDevicePtr",
     "idkptSetPresentationSize", "idkptGetPresentationSize", "idkptGetBloomRoute", "idkptGetBloomChainDevicePtr",
     "idkptCollideSpheres", "idkptCollideSpheresDevice",
-    "idkptDenoise", "idkptUploadDenoised", "idkptDownloadDenoised", "idkptGetDenoisedDevicePtr", "idkptGetDenoiseRoute", "idkptSetResultSource", "idkptGetResultSource",
+    "idkptDenoise", "idkptUploadDenoised", "idkptDownloadDenoised", "idkptGetDenoisedDevicePtr", "idkptGetDenoiseRoute", "idkptSetResultSource", "idkptGetResultSource", "idkptDenoiseVariance",
     "idkptSetNoiseEstimate", "idkptGetNoiseEstimate", "idkptEstimateNoise", "idkptDownloadNoise", "idkptGetNoiseDevicePtr", "idkptDownloadMoments", "idkptGetMomentsDevicePtr",
 ]
 
@@ -53,7 +53,7 @@ def load():
         "idkptSetPresentationSize": [vp, i32, i32], "idkptGetPresentationSize": [vp, C.POINTER(i32), C.POINTER(i32)], "idkptGetBloomRoute": [vp, i32, C.POINTER(i32)], "idkptGetBloomChainDevicePtr": [vp, i32, i32, C.POINTER(vp), C.POINTER(sz)],
         "idkptCollideSpheres": [vp, vp, vp, sz, vp], "idkptCollideSpheresDevice": [vp, vp, vp, sz, vp],
         "idkptDenoise": [vp, i32, vp], "idkptUploadDenoised": [vp, i32, vp, sz], "idkptDownloadDenoised": [vp, i32, vp, sz], "idkptGetDenoisedDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(sz)], "idkptGetDenoiseRoute": [vp, i32, i32, C.POINTER(i32)],
-        "idkptSetResultSource": [vp, i32], "idkptGetResultSource": [vp, C.POINTER(i32)],
+        "idkptSetResultSource": [vp, i32], "idkptGetResultSource": [vp, C.POINTER(i32)], "idkptDenoiseVariance": [vp, i32, vp],
         "idkptSetNoiseEstimate": [vp, i32], "idkptGetNoiseEstimate": [vp, C.POINTER(i32)], "idkptEstimateNoise": [vp, i32, vp], "idkptDownloadNoise": [vp, i32, vp, sz, vp],
         "idkptGetNoiseDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(sz)], "idkptDownloadMoments": [vp, i32, vp, sz], "idkptGetMomentsDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(sz)],
         "idkptRefitBlas": [vp, i32], "idkptUploadUnskinnedVertices": [vp, vp, i32], "idkptSkin": [vp, u32, u32, u32, u32],

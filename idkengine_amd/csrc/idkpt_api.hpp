@@ -900,6 +900,7 @@ int32_t idkptUploadDenoised(idkpt_ctx* c, int32_t slot, const float* rgba, size_
 int32_t idkptDownloadDenoised(idkpt_ctx* c, int32_t slot, float* rgba, size_t bytes) { ONE_ONLY("idkptDownloadDenoised", DENOISE_WHY, dev_DownloadDenoised(m, slot, rgba, bytes)); }
 int32_t idkptGetDenoisedDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size_t* outBytes) { ONE_ONLY("idkptGetDenoisedDevicePtr", DENOISE_WHY, dev_GetDenoisedDevicePtr(m, slot, outPtr, outBytes)); }
 int32_t idkptGetDenoiseRoute(idkpt_ctx* c, int32_t slot, int32_t iteration, int32_t* outRoute) { ONE_ONLY("idkptGetDenoiseRoute", DENOISE_WHY, dev_GetDenoiseRoute(m, slot, iteration, outRoute)); }
+int32_t idkptDenoiseVariance(idkpt_ctx* c, int32_t slot, const idkpt_denoise_variance* settings) { ONE_ONLY("idkptDenoiseVariance", DENOISE_WHY, dev_DenoiseVariance(m, slot, settings)); }
 // the result source: a multi-device context stays at IDKPT_RESULT_NOISY (its members never look at anything else)
 int32_t idkptSetResultSource(idkpt_ctx* c, int32_t source)
 {

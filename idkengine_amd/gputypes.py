@@ -200,6 +200,15 @@ class Denoise(C.Structure):
         super().__init__(int(Iterations), float(ColorSigma), float(AlbedoSigma), float(NormalSigma), int(DemodulateAlbedo))
 
 
+class DenoiseVariance(C.Structure):
+    """idkpt_denoise_variance: the settings of idkptDenoiseVariance (include/idkpt.h, "variance-guided denoised output"; no counterpart in the reference).  The LumaSigma
+    and VarianceEpsilon defaults are the tuned ones of profiles/denoise_variance.md."""
+    _fields_ = [("Iterations", C.c_int32), ("LumaSigma", C.c_float), ("VarianceEpsilon", C.c_float), ("AlbedoSigma", C.c_float), ("NormalSigma", C.c_float), ("DemodulateAlbedo", C.c_int32)]
+
+    def __init__(self, Iterations=5, LumaSigma=1.0, VarianceEpsilon=0.1, AlbedoSigma=0.2, NormalSigma=0.5, DemodulateAlbedo=True):
+        super().__init__(int(Iterations), float(LumaSigma), float(VarianceEpsilon), float(AlbedoSigma), float(NormalSigma), int(DemodulateAlbedo))
+
+
 class Noise(C.Structure):
     """idkpt_noise: the settings of idkptEstimateNoise (include/idkpt.h, "noise estimate"; no counterpart in the reference).  The defaults are starting values nobody has
     tuned (profiles/noise.md)."""

@@ -603,6 +603,18 @@ class PathTracer:
         self._check(self._L.idkptDenoise(self._ctx, slot, C.addressof(settings)))
         return self.DownloadDenoised(slot)
 
+    def DenoiseVariance(self, settings=None, slot=None):
+        """idkptDenoiseVariance + idkptDownloadDenoised: the variance-guided a-trous filter of include/idkpt.h over Result of ring slot `slot` (None: the current one), guided
+        by Albedo, Normal and the luminance moments (needs OutputAOVs, SetNoiseEstimate(True) and 2 accumulated samples), as an (H, W, 4) float32 array (rgb, 1.0).
+        settings: a gputypes.DenoiseVariance; None = the defaults.  It fills the image Denoise fills: Present and Bloom read it under IDKPT_RESULT_DENOISED."""
+        if settings is None:
+            settings = T.DenoiseVariance()
+        if not isinstance(settings, T.DenoiseVariance):
+            raise TypeError("DenoiseVariance: settings must be a gputypes.DenoiseVariance")
+        slot = -1 if slot is None else int(slot)
+        self._check(self._L.idkptDenoiseVariance(self._ctx, slot, C.addressof(settings)))
+        return self.DownloadDenoised(slot)
+
     def UploadDenoised(self, rgba, slot=None):
         """idkptUploadDenoised: the host's own denoiser's output, an (H, W, 4) float32 array, becomes the denoised image of the slot (the reference's denoisedTexture.Upload2D)"""
         rgba = np.ascontiguousarray(rgba, np.float32)

@@ -243,7 +243,7 @@ typedef struct idkpt_stats {
  * 7 = idkptBloom / idkptGetBloomInfo / idkptDownloadBloom / idkptGetBloomDevicePtr, 8 = idkptUnprojectSky,
  * 9 = idkptSetPresentationSize / idkptGetPresentationSize / idkptGetBloomRoute / idkptGetBloomChainDevicePtr, 10 = idkptDownloadTileClasses, 11 = idkptCollideSpheres / idkptCollideSpheresDevice,
  * 12 = idkptDenoise / idkptUploadDenoised / idkptDownloadDenoised / idkptGetDenoisedDevicePtr / idkptGetDenoiseRoute / idkptSetResultSource / idkptGetResultSource).  The noise-estimate entry points (idkptSetNoiseEstimate ... idkptGetMomentsDevicePtr, below) were added WITHOUT a new number: nothing a host of ABI 12 can
- * trip over changed, and a host that wants them looks the symbols up (dlsym / GetProcAddress: a library without them has none of the seven).  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
+ * trip over changed, and a host that wants them looks the symbols up (dlsym / GetProcAddress: a library without them has none of the seven); idkptDenoiseVariance was added the same way.  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
  * of ITS struct to idkptGetStatsSized and gets exactly that many bytes; idkptGetStats(ctx, out) is idkptGetStatsSized(ctx, out, sizeof(idkpt_stats)) of the header the LIBRARY
  * was built with — for hosts built from the same tree.  idkptGetAbiVersion() lets a host refuse a library older than the header it was written against. */
 #define IDKPT_ABI_VERSION 12
@@ -745,6 +745,61 @@ IDKPT_API int32_t idkptDownloadNoise(idkpt_ctx* ctx, int32_t slot, float* tiles,
 IDKPT_API int32_t idkptGetNoiseDevicePtr(idkpt_ctx* ctx, int32_t slot, void** outTiles, void** outSummary, size_t* outTileBytes);
 IDKPT_API int32_t idkptDownloadMoments(idkpt_ctx* ctx, int32_t slot, float* rgba, size_t bytes);
 IDKPT_API int32_t idkptGetMomentsDevicePtr(idkpt_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes);   /* stream-ordered; the guard bytes follow *outBytes */
+
+/* ---- variance-guided denoised output (added under ABI 12; detect by symbol): the a-trous filter steered by the luminance moments -----------------------------------------
+ * THIS HAS NO COUNTERPART IN THE REFERENCE.  idkptDenoise's colour range kernel does not know how noisy a pixel is: one ColorSigma, halved every iteration, for a converged
+ * region and for a firefly-ridden one.  idkptDenoiseVariance is the same filter (taps, guides, demodulation) with SVGF's remedy (Schied et al. 2017): the range kernel
+ * works on LUMINANCE and its width follows the variance of the pixel's mean luminance, which the moments image of the noise estimate (above) provides and which the filter
+ * carries from iteration to iteration.  A third way to fill the slot's denoised image: idkptDownloadDenoised, idkptGetDenoisedDevicePtr, idkptGetDenoiseRoute,
+ * idkptSetResultSource, idkptPresent and idkptBloom work on its result as on idkptDenoise's; the buffers are the same (the variance travels in the alpha channel of the two
+ * images the iterations alternate between) and so are their life cycle and guard bytes.  idkptDenoise and its result are unchanged by a bit.
+ * Every operation is a correctly rounded binary32 + - * / in the written order (-ffp-contract=off), so the text below defines the result BIT FOR BIT; it is checked
+ * against an independent numpy restatement (tests/denoise_variance_ref.py).  The weights are defined so that a tap costs ONE division (idkptDenoise's contract: three).
+ *
+ *   lum(u) = (0.2126f * u.x + 0.7152f * u.y) + 0.0722f * u.z          (the luminance of the noise estimate)
+ *   floor(a) = fmaxf(a, 1e-3f) per channel                            (the albedo floor of idkptDenoise)
+ * Inputs per pixel.  c0 = Result.rgb, a = Albedo.rgb, n = Normal.rgb of the slot as accumulated; (m1, m2) of the slot's moments image; N = the slot's accumulated sample
+ * count (queued samples included).
+ *   v0 = fmaxf(m2 - m1 * m1, 0.0f) / (float)(N - 1)                   the variance of the pixel's mean luminance; v0 = +Inf if m1 or m2 is not finite.
+ *   If DemodulateAlbedo: c0 = c0 / floor(a) per channel; la = lum(floor(a)); v0 = v0 / (la * la).
+ * State.  (c.rgb, v) per pixel, (c0, v0) before the first iteration.
+ * Iteration i = 0 .. Iterations - 1, spacing s = 1 << i, at every pixel p:
+ *   1. If v_p is not finite the pixel is unchanged: out = (c_p, v_p).
+ *   2. The prefiltered variance g: taps p + (ex, ey), ex and ey in -1 .. 1 (spacing 1 whatever s is), ey the outer loop, ex the inner one;
+ *      gw = b[ex + 1] * b[ey + 1], b = { 1/4, 1/2, 1/4 }; a tap outside the image or with a v that is not finite is SKIPPED;
+ *      sumGV += gw * v_q, sumG += gw; g = sumGV / sumG.
+ *   3. invL = 1 / ((LumaSigma * LumaSigma) * g + VarianceEpsilon).  LumaSigma * LumaSigma, invA = 1 / (AlbedoSigma * AlbedoSigma) and invN = 1 / (NormalSigma * NormalSigma)
+ *      are computed once per call on the host in binary32 (invA and invN are idkptDenoise's values).  LumaSigma does NOT halve.
+ *   4. Taps q = p + s * (dx, dy), dy the outer loop over -2 .. 2, dx the inner one, all sums accumulated in that order; a tap outside the image is SKIPPED;
+ *      h = k[dx + 2] * k[dy + 2], k = { 1/16, 1/4, 3/8, 1/4, 1/16 };   d(u) = u_q - u_p, |d|^2 = (d.x * d.x + d.y * d.y) + d.z * d.z;
+ *      dl = lum(c_q) - lum(c_p);
+ *      den = ((1 + (dl * dl) * invL) * (1 + |d(a)|^2 * invA)) * (1 + |d(n)|^2 * invN);
+ *      w = h / den;
+ *      the tap contributes only if w > 0 and v_q is finite: sum += c_q * w per channel, sumV += v_q * (w * w), sumW += w.
+ *   5. c_out = sum / sumW per channel, v_out = sumV / (sumW * sumW); if sumW == 0, out = (c_p, v_p) unchanged.
+ * After the last iteration, if DemodulateAlbedo: c = c * floor(a).  The alpha stored in the denoised image is 1.0 (the variance is not returned).
+ * Non-finite values.  No value feeds an address.  `w > 0` is false for a NaN weight and for the zero weight of an overflowed difference, so a texel or guide that is not
+ * finite contributes to no neighbour's 25 taps, and a pixel that is NaN or infinite itself (colour or guide) drops every tap and keeps its colour and variance.  A pixel
+ * whose variance is not finite (a moment that is not finite) is left as it is and appears in no neighbour's sums, prefilter included: every other pixel is what it would
+ * be with that pixel outside the image.  (The variance of a pixel whose COLOUR is not finite stays in its neighbours' prefilter: the prefilter looks at v alone.)
+ *
+ * The call behaves as idkptDenoise does: slot -1 is the current slot; queued samples are launched first; the call is stream-ordered and waits for nothing; ONE device that
+ * holds the WHOLE frame; OutputAOVs != 0.  It reads Result, Albedo, Normal and the moments and changes none of them, nor the accumulation.  idkptGetDenoiseRoute answers
+ * for its iterations (spacing 1, 2, 4: TILED; 8 and up: DIRECT).
+ * IDKPT_ERR_INVALID_OPERATION, before anything is launched: the noise-estimate switch is off (idkptSetNoiseEstimate: no moments are kept); the slot has accumulated N < 2
+ * samples; no size set; a context without the whole frame; OutputAOVs == 0.  IDKPT_ERR_INVALID_ARGUMENT, before anything is launched: a slot outside the ring, Iterations
+ * outside 1..8, a LumaSigma, VarianceEpsilon, AlbedoSigma or NormalSigma that is not finite and > 0, DemodulateAlbedo other than 0 / 1, a NULL pointer.  A refused call
+ * leaves the slot's previous denoised image valid and untouched.
+ * The LumaSigma and VarianceEpsilon defaults (1.0, 0.1) are the minimum of a sweep on one small render at two sample counts (profiles/denoise_variance.md). */
+typedef struct idkpt_denoise_variance {
+    int32_t Iterations;        /* 1..8; iteration i uses tap spacing 1 << i.  default 5 */
+    float   LumaSigma;         /* > 0, finite; in standard deviations of the (demodulated) mean luminance; does NOT halve per iteration.  default 1.0 (tuned: profiles/denoise_variance.md) */
+    float   VarianceEpsilon;   /* > 0, finite; the squared luminance difference a converged pixel (g = 0) tolerates at half weight.  default 0.1 (tuned: profiles/denoise_variance.md) */
+    float   AlbedoSigma;       /* > 0, finite.  default 0.2 */
+    float   NormalSigma;       /* > 0, finite.  default 0.5 */
+    int32_t DemodulateAlbedo;  /* 0 / 1.  default 1 */
+} idkpt_denoise_variance;
+IDKPT_API int32_t idkptDenoiseVariance(idkpt_ctx* ctx, int32_t slot, const idkpt_denoise_variance* settings);   /* Result, Albedo, Normal and the moments of the slot -> its denoised image */
 
 /* ---- render ----------------------------------------------------------------------------- */
 /* PathTracer.ResetAccumulation (PathTracer.cs:334-337) */
