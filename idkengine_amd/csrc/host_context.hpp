@@ -243,6 +243,8 @@ struct dev_ctx {
     std::vector<uint32_t> levelBase;                 // per BLAS base into levelNodes
     std::vector<char> refitCoversAll;                // per BLAS: leaves + internal nodes of the refit schedule are every node but node 0 (a refit into a fresh slot needs no copy of the old nodes)
     int nodeCount = 0, triCount = 0, instanceCount = 0, tlasCount = 0, vertexCount = 0, meshCount = 0, materialCount = 0, xformCount = 0, lightCount = 0, skySize = 0, textureCount = 0, unskinnedCount = 0;
+    size_t skinMaxFirst = 0, skinMaxCount = 0; uint32_t skinMaxValue = 0;   // the last range idkptSkin asked about and its answer (an animated host asks for the same range every frame)
+    std::vector<uint32_t> unskinnedMaxJoint, unskinnedBlockMaxJoint;   // per unskinned vertex the largest of its four JointIndices, and the maxima of blocks of 256 vertices: idkptSkin's joint-table check without a scan per frame
     int sceneStack = 1;
     int hInst0Blas = 0;                              // BlasId of instance 0 (MODE 0 traverses that BLAS)
     // wide nodes (kernels_wide.hpp): derived per BLAS from nodes + triVerts.  wideTopoValid: the children lists match the node topology; wideFillValid: boxes / leaf records match the current boxes and positions

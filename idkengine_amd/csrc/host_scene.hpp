@@ -875,6 +875,14 @@ static int32_t dev_DownloadBuffer(dev_ctx* ctx, int32_t which, size_t offsetByte
         HIPC(hipStreamSynchronize(ctx->stream));
         return IDKPT_OK;
     }
+    if (which == IDKPT_BUF_PREV_VERTEX_POSITIONS) {   // what idkptSkin kept of the positions it replaced (update kernels only: stream order, nothing queued reads it)
+        if (!ctx->haveScene || !ctx->prevPositions.p) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptDownloadBuffer: no previous positions before the first idkptSkin");
+        REQUIRE(offsetBytes + bytes <= (size_t)ctx->vertexCount * 12, "idkptDownloadBuffer: bad buffer/range");
+        HIPC(hipSetDevice(ctx->device));
+        HIPC(hipMemcpyAsync(dst, (char*)ctx->prevPositions.p + offsetBytes, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIPC(hipStreamSynchronize(ctx->stream));
+        return IDKPT_OK;
+    }
     size_t cap = 0; int vb = -1; DevBuf* b = which_buffer(ctx, which, &cap, &vb);
     REQUIRE(b != nullptr && offsetBytes + bytes <= cap, "idkptDownloadBuffer: bad buffer/range");
     HIPC(hipSetDevice(ctx->device));
@@ -964,7 +972,30 @@ static int32_t dev_UploadUnskinnedVertices(dev_ctx* ctx, const GpuUnskinnedVerte
     int rc = upload(ctx, ctx->unskinned, verts, (size_t)count * sizeof(GpuUnskinnedVertex)); if (rc) return rc;
     HIPC(hipStreamSynchronize(ctx->stream));
     ctx->unskinnedCount = count;
+    // what idkptSkin needs to refuse a joint outside the table without reading the vertices again: each vertex's largest index, and the maxima of blocks of 256
+    ctx->skinMaxCount = 0;
+    ctx->unskinnedMaxJoint.resize((size_t)count); ctx->unskinnedBlockMaxJoint.assign(((size_t)count + 255) / 256, 0u);
+    for (size_t i = 0; i < (size_t)count; i++) {
+        const uint32_t* j = verts[i].JointIndices;
+        const uint32_t m = std::max(std::max(j[0], j[1]), std::max(j[2], j[3]));
+        ctx->unskinnedMaxJoint[i] = m; ctx->unskinnedBlockMaxJoint[i / 256] = std::max(ctx->unskinnedBlockMaxJoint[i / 256], m);
+    }
     return IDKPT_OK;
+}
+
+// the largest joint index any vertex of [first, first + count) holds (count > 0, range inside the table): whole blocks of 256 through their maxima, the two ragged ends vertex by vertex
+static uint32_t unskinned_max_joint(dev_ctx* ctx, size_t first, size_t count)
+{
+    if (first == ctx->skinMaxFirst && count == ctx->skinMaxCount) return ctx->skinMaxValue;
+    const size_t end = first + count;
+    uint32_t m = 0;
+    size_t i = first;
+    while (i < end) {
+        if (i % 256 == 0 && i + 256 <= end) { m = std::max(m, ctx->unskinnedBlockMaxJoint[i / 256]); i += 256; }
+        else { m = std::max(m, ctx->unskinnedMaxJoint[i]); i++; }
+    }
+    ctx->skinMaxFirst = first; ctx->skinMaxCount = count; ctx->skinMaxValue = m;
+    return m;
 }
 
 static int32_t dev_Skin(dev_ctx* ctx, uint32_t inOff, uint32_t outOff, uint32_t jointOff, uint32_t count)
@@ -972,8 +1003,16 @@ static int32_t dev_Skin(dev_ctx* ctx, uint32_t inOff, uint32_t outOff, uint32_t 
     if (!ctx) return IDKPT_ERR_INVALID_ARGUMENT;
     if (!ctx->haveScene || ctx->unskinnedCount == 0 || ctx->joints.bytes == 0) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptSkin: needs scene, unskinned vertices and joint matrices");
     REQUIRE((uint64_t)inOff + count <= (uint64_t)ctx->unskinnedCount && (uint64_t)outOff + count <= (uint64_t)ctx->vertexCount, "idkptSkin: range out of bounds");
+    if (count) {
+        // k_skin reads joints[jointOff + JointIndices[k]] for all four indices of every vertex of the range, whatever their weights: none may leave the resident table
+        const uint64_t jointCount = ctx->joints.bytes / 48, reach = (uint64_t)jointOff + unskinned_max_joint(ctx, inOff, count);
+        REQUIRE(reach < jointCount, "idkptSkin: a vertex of the range addresses joint " + std::to_string(reach) + " (jointMatricesOffset + JointIndices), the joint table holds " + std::to_string(jointCount));
+    }
     HIPC(hipSetDevice(ctx->device));
-    HIPC(ctx->prevPositions.ensure((size_t)ctx->vertexCount * 12));
+    if (ctx->prevPositions.bytes < (size_t)ctx->vertexCount * 12 || !ctx->prevPositions.p) {   // (entries no call has written read as zero: IDKPT_BUF_PREV_VERTEX_POSITIONS)
+        HIPC(ctx->prevPositions.ensure((size_t)ctx->vertexCount * 12));
+        HIPC(hipMemsetAsync(ctx->prevPositions.p, 0, ctx->prevPositions.bytes, ctx->stream));
+    }
     // positions are read by update kernels only (stream order); the re-compressed normals / tangents go to a vertex slot no queued sample reads (ver_writable)
     char *vsrc, *vdst; { int rc = ver_writable(ctx, VB_VERTICES, outOff == 0 && count == (uint32_t)ctx->vertexCount, &vsrc, &vdst); if (rc) return rc; }
     if (count) hipLaunchKernelGGL(k_skin, dim3((count + 63) / 64), dim3(64), 0, ctx->stream, ctx->unskinned.as<GpuUnskinnedVertex>(), ctx->joints.as<float4>(), ctx->positions.as<float>(),

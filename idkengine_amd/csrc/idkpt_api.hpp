@@ -82,6 +82,7 @@ struct idkpt_ctx {
     std::string lastError;
     idkpt_error_fn errFn = nullptr; void* errUser = nullptr;
     PeerPolicy peer;                                        // how the members copy to each other (xGMI peer copies, or staged through the host)
+    int downloadMember = 0;                                  // option "download_member": whose copy of a scene buffer idkptDownloadBuffer reads (tests: every member holds the same bytes)
     RcclTransport rccl; int transportOpt = 0;               // option "transport": 0 = RCCL where it can be formed, else peer copies; 1 = peer copies; 2 = RCCL or fail (transport_rccl.hpp)
     hipEvent_t evGatherStart = nullptr;                     // device 0: what was queued on its stream before a gather (the consumer of the previous frame)
     bool frameOk = true;                                    // false after a failed re-layout: idkptRender refuses until the next successful idkptSetSize
@@ -623,6 +624,11 @@ int32_t idkptSetDeveloperOption(idkpt_ctx* c, const char* name, int32_t value)
 {
     if (!c || !name) return IDKPT_ERR_INVALID_ARGUMENT;
     if (c->n() > 1 && std::string(name) == "force_no_peer") { GFLUSH(); c->peer.forceStaged = value != 0; return IDKPT_OK; }   // device-to-device copies through pinned host memory
+    if (std::string(name) == "download_member") {                                                                             // which member's copy idkptDownloadBuffer reads (0: the first)
+        GREQ(value >= 0 && value < (int)c->n(), "idkptSetDeveloperOption: download_member is a member index of the context");
+        c->downloadMember = value;
+        return IDKPT_OK;
+    }
     if (std::string(name) == "transport") {                                                                                   // how the members' bulk traffic travels (transport_rccl.hpp)
         GREQ(value >= 0 && value <= 2, "idkptSetDeveloperOption: transport is 0 (RCCL where usable), 1 (peer copies) or 2 (RCCL required)");
         if (c->n() > 1) GFLUSH();
@@ -663,8 +669,9 @@ int32_t idkptDownloadBuffer(idkpt_ctx* c, int32_t which, size_t offsetBytes, siz
     if (!c) return IDKPT_ERR_INVALID_ARGUMENT;
     ONE(dev_DownloadBuffer(m, which, offsetBytes, bytes, dst));
     GFLUSH();
-    int rc = dev_DownloadBuffer(c->dev[0], which, offsetBytes, bytes, dst);       // the scene is replicated: any member's copy
-    return rc ? mfail(c, c->dev[0], rc) : IDKPT_OK;
+    dev_ctx* from = c->dev[(size_t)c->downloadMember];                            // the scene is replicated: any member's copy (the first unless option "download_member" names another)
+    int rc = dev_DownloadBuffer(from, which, offsetBytes, bytes, dst);
+    return rc ? mfail(c, from, rc) : IDKPT_OK;
 }
 
 int32_t idkptDownloadTexture(idkpt_ctx* c, int32_t index, int32_t* outResidentFormat, int32_t* outWidth, int32_t* outHeight, void* dst, size_t dstBytes)

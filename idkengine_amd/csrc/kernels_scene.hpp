@@ -445,6 +445,8 @@ __global__ __launch_bounds__(256) void k_pair_nodes(const float4* blasNodes, con
 // atomicExchange "second arrival" lock; here the same unions are evaluated level by level (deepest first), one launch
 // per level, so no workgroup ever consumes another workgroup's stores inside a launch (per-XCD L2s are not coherent).
 // (src: the node array being replaced — topology words; nodes: the array being written — the same array unless the refit goes to another scene-version slot)
+// Unions are Box.GrowToFit's (Shapes/Box.cs:40-50): minps / maxps, (a < b) ? a : b in the order (accumulated box, new point) and (left child, right child) — equal operands,
+// +0 against -0 among them, give the SECOND.  v_min_f32 / v_max_f32 order the zeros instead (-0 < +0) and would store another sign there.
 __global__ void k_refit_leaves(const float4* src, float4* nodes, const uint4* tris, const float4* triVerts, const int32_t* leafIds, uint32_t leafCount, uint32_t nodeOffset, uint32_t triOffset)
 {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -454,7 +456,7 @@ __global__ void k_refit_leaves(const float4* src, float4* nodes, const uint4* tr
     uint32_t start = triOffset + __float_as_uint(mn.w), count = __float_as_uint(mx.w);
     f3 bmin = splat3(PT_FLOAT_MAX), bmax = splat3(-PT_FLOAT_MAX);
     for (uint32_t k = start; k < start + count; k++) {
-        for (int v = 0; v < 3; v++) { float4 p = triVerts[3 * (size_t)k + v]; bmin = mk3(gmin(bmin.x, p.x), gmin(bmin.y, p.y), gmin(bmin.z, p.z)); bmax = mk3(gmax(bmax.x, p.x), gmax(bmax.y, p.y), gmax(bmax.z, p.z)); }
+        for (int v = 0; v < 3; v++) { float4 p = triVerts[3 * (size_t)k + v]; bmin = mk3(tlas_minN(bmin.x, p.x), tlas_minN(bmin.y, p.y), tlas_minN(bmin.z, p.z)); bmax = mk3(tlas_maxN(bmax.x, p.x), tlas_maxN(bmax.y, p.y), tlas_maxN(bmax.z, p.z)); }
     }
     nodes[2 * (size_t)id] = make_float4(bmin.x, bmin.y, bmin.z, mn.w); nodes[2 * (size_t)id + 1] = make_float4(bmax.x, bmax.y, bmax.z, mx.w);
 }
@@ -466,8 +468,8 @@ __global__ void k_refit_level(const float4* src, float4* nodes, const int32_t* l
     float4 mn = src[2 * (size_t)id], mx = src[2 * (size_t)id + 1];
     uint32_t child = nodeOffset + __float_as_uint(mn.w);
     float4 lmn = nodes[2 * (size_t)child], lmx = nodes[2 * (size_t)child + 1], rmn = nodes[2 * (size_t)child + 2], rmx = nodes[2 * (size_t)child + 3];
-    nodes[2 * (size_t)id] = make_float4(gmin(lmn.x, rmn.x), gmin(lmn.y, rmn.y), gmin(lmn.z, rmn.z), mn.w);
-    nodes[2 * (size_t)id + 1] = make_float4(gmax(lmx.x, rmx.x), gmax(lmx.y, rmx.y), gmax(lmx.z, rmx.z), mx.w);
+    nodes[2 * (size_t)id] = make_float4(tlas_minN(lmn.x, rmn.x), tlas_minN(lmn.y, rmn.y), tlas_minN(lmn.z, rmn.z), mn.w);
+    nodes[2 * (size_t)id + 1] = make_float4(tlas_maxN(lmx.x, rmx.x), tlas_maxN(lmx.y, rmx.y), tlas_maxN(lmx.z, rmx.z), mx.w);
 }
 
 // Skinning (Shaders/Skinning/compute.glsl:14-47): 4-weight linear blend; joint matrices are row_major mat4x3 (3 x float4)

@@ -130,7 +130,9 @@ DEV f3 DecompressSR11G11B10(uint32_t d)
 DEV uint32_t CompressSR11G11B10(f3 d)
 {
     f3 u = mk3(d.x * 0.5f + 0.5f, d.y * 0.5f + 0.5f, d.z * 0.5f + 0.5f);
-    uint32_t r = (uint32_t)__builtin_rintf(u.x * 2047.0f), g = (uint32_t)__builtin_rintf(u.y * 2047.0f), b = (uint32_t)__builtin_rintf(u.z * 1023.0f);
+    // each field is clamped to its own range before the cast, NaN acting as 0 (fmaxf / fminf return the other operand; kernels_present.hpp does the same): a cast of NaN, of a
+    // negative value or of +-Inf has no defined result, and a code beyond its field would spill into the next one (idkpt.h, idkptSkin).  Components in [-1, 1] are unchanged.
+    uint32_t r = (uint32_t)__builtin_rintf(gmin(gmax(u.x * 2047.0f, 0.0f), 2047.0f)), g = (uint32_t)__builtin_rintf(gmin(gmax(u.y * 2047.0f, 0.0f), 2047.0f)), b = (uint32_t)__builtin_rintf(gmin(gmax(u.z * 1023.0f, 0.0f), 1023.0f));
     return (b << 22) | (g << 11) | r;
 }
 DEV f2 EncodeUnitVec(f3 n)

@@ -52,6 +52,9 @@ enum idkpt_buffer {
     IDKPT_BUF_WIDE_NODES = 9,      /* 64-byte wide nodes, BLAS b at 64 * (sum over earlier BLASes of NodeCount / 2 + 1) */
     IDKPT_BUF_WIDE_LEAVES = 10,    /* leaf records, 16-byte units */
     IDKPT_BUF_WIDE_COUNTS = 11,    /* per BLAS: uint32 wide nodes in use, uint32 16-byte units of leaf records in use */
+    /* idkptDownloadBuffer only (ABI 13) — what idkptSkin keeps of the positions it replaced (Skinning/compute.glsl:44, SSBO 9): packed float3 per vertex, VertexCount entries.
+     * IDKPT_ERR_INVALID_OPERATION before the first idkptSkin; entries no idkptSkin has written yet read as zero. */
+    IDKPT_BUF_PREV_VERTEX_POSITIONS = 12,
 };
 
 /* One image of the texture table + the sampler state it is sampled with (stand-in for the GL bindless samplers of GpuMaterial: a texture object and the GLSampler.SamplerState
@@ -242,11 +245,12 @@ typedef struct idkpt_stats {
  * enum values of idkpt_buffer or idkpt_texture_format, new fields of idkpt_texture, new entry points: 5 = idkptComputeSky / idkptUpdateSky / idkptDownloadSky, 6 = idkptPresent / idkptDownloadDisplay / idkptGetDisplayDevicePtr,
  * 7 = idkptBloom / idkptGetBloomInfo / idkptDownloadBloom / idkptGetBloomDevicePtr, 8 = idkptUnprojectSky,
  * 9 = idkptSetPresentationSize / idkptGetPresentationSize / idkptGetBloomRoute / idkptGetBloomChainDevicePtr, 10 = idkptDownloadTileClasses, 11 = idkptCollideSpheres / idkptCollideSpheresDevice,
- * 12 = idkptDenoise / idkptUploadDenoised / idkptDownloadDenoised / idkptGetDenoisedDevicePtr / idkptGetDenoiseRoute / idkptSetResultSource / idkptGetResultSource).  The noise-estimate entry points (idkptSetNoiseEstimate ... idkptGetMomentsDevicePtr, below) were added WITHOUT a new number: nothing a host of ABI 12 can
+ * 12 = idkptDenoise / idkptUploadDenoised / idkptDownloadDenoised / idkptGetDenoisedDevicePtr / idkptGetDenoiseRoute / idkptSetResultSource / idkptGetResultSource,
+ * 13 = IDKPT_BUF_PREV_VERTEX_POSITIONS).  The noise-estimate entry points (idkptSetNoiseEstimate ... idkptGetMomentsDevicePtr, below) were added WITHOUT a new number: nothing a host of ABI 12 can
  * trip over changed, and a host that wants them looks the symbols up (dlsym / GetProcAddress: a library without them has none of the seven); idkptDenoiseVariance was added the same way.  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
  * of ITS struct to idkptGetStatsSized and gets exactly that many bytes; idkptGetStats(ctx, out) is idkptGetStatsSized(ctx, out, sizeof(idkpt_stats)) of the header the LIBRARY
  * was built with — for hosts built from the same tree.  idkptGetAbiVersion() lets a host refuse a library older than the header it was written against. */
-#define IDKPT_ABI_VERSION 12
+#define IDKPT_ABI_VERSION 13
 
 /* ---- lifetime --------------------------------------------------------------------------- */
 /* new PathTracer(w,h,settings) (PathTracer.cs:170-212).  deviceCount = 1: the reference's situation, one GPU.
@@ -446,7 +450,21 @@ IDKPT_API int32_t idkptCbrtProbe(idkpt_ctx* ctx, const float* in, float* out, in
 /* BVH.GpuBlasesRefit(blasId,1) (Bvh/BVH.cs:472-489, Shaders/BLASRefit/compute.glsl) */
 IDKPT_API int32_t idkptRefitBlas(idkpt_ctx* ctx, int32_t blasId);
 /* ModelManager skinning dispatch (ModelManager.cs:326-353, Shaders/Skinning/compute.glsl):
- * skins vertexCount vertices from unskinned[inputOffset..] into positions/vertices[outputOffset..] */
+ * skins vertexCount vertices from unskinned[inputOffset..] into positions/vertices[outputOffset..].  Vertex i of the range blends the four joint matrices
+ * jointMatricesOffset + JointIndices[k] with JointWeights[k] AS GIVEN (no normalisation: weights that sum to 4 scale the position by 4, all-zero weights give the
+ * zero matrix), every operation in binary32 in the shader's order.  Outside the range nothing is written: positions, the previous positions and all four words of
+ * every vertex keep their values; inside it the two uv words of a vertex are copied and only its normal and tangent words change.  The previous-position array
+ * (IDKPT_BUF_PREV_VERTEX_POSITIONS) receives the positions the call replaces, for the vertices of the range ONLY — it is not a copy of the whole array.
+ * Refused with IDKPT_ERR_INVALID_ARGUMENT, before anything is launched or changed: a range that leaves the unskinned table or the scene's vertices, and a range in which
+ * any vertex addresses a joint outside the resident joint table — jointMatricesOffset + JointIndices[k] >= (bytes of IDKPT_BUF_JOINT_MATRICES uploaded so far) / 48 for any
+ * of its four indices, the sum taken without wrapping (a weight of 0 does not excuse the index: the shader reads the matrix all the same).  Vertices outside the range
+ * never refuse a call, and vertexCount == 0 succeeds and touches nothing.  The check costs the host O(vertexCount / 256): idkptUploadUnskinnedVertices keeps each vertex's
+ * largest index and the maxima of blocks of 256.
+ * Compression of the skinned normal / tangent v (Compression.glsl CompressSR11G11B10): u = v * 0.5 + 0.5 per component, code = rint(u * 2047) (x, y) or rint(u * 1023) (z),
+ * ties to even, word = z << 22 | y << 11 | x.  Values no field can hold follow ONE rule: u * 2047 (1023) is clamped to [0, 2047] ([0, 1023]) before the conversion and NaN
+ * acts as 0 (fminf(fmaxf(x, 0), max)), so NaN -> 0, -Inf -> 0, +Inf -> all ones of that field, and no field ever spills into its neighbour.  Such values are what the
+ * arithmetic gives for degenerate input: all-zero weights or a singular joint (normalize(0) = NaN), a joint scale near 1e-30 (the squared length underflows: v * (1 / 0) =
+ * +-Inf, or NaN where a component is 0), NaN / Inf joint entries.  Finite components lie in [-1, 1] after the normalisation and store exactly what the shader stores. */
 IDKPT_API int32_t idkptUploadUnskinnedVertices(idkpt_ctx* ctx, const GpuUnskinnedVertex* verts, int32_t count);
 IDKPT_API int32_t idkptSkin(idkpt_ctx* ctx, uint32_t inputVertexOffset, uint32_t outputVertexOffset, uint32_t jointMatricesOffset, uint32_t vertexCount);
 /* Batched ray queries through the same BVH/TLAS/light data and the same traversal code as the path tracer (uses the context's
@@ -909,6 +927,7 @@ IDKPT_API int32_t idkptEnableTiming(idkpt_ctx* ctx, int32_t enable);
  *   multi-device contexts
  *     "transport"        0* / 1 / 2  RCCL where usable / peer copies / RCCL or fail (idkptGetTransportInfo)      "force_no_peer" 0* / 1   stage device-to-device copies through pinned host memory
  *     "group_threads"    -1* / 0 / 1 members' batches enqueued by one host thread each (-1: from 4 members on)
+ *     "download_member"  0* .. N - 1 the member whose copy idkptDownloadBuffer reads (the scene is replicated: tests hold every member's bytes to the same answer)
  *   builder                "bvh_timing" 0* / 1 (phase times on stderr), "bvh_small" (32*), "bvh_stackopt_host" 0* / 1 (force the host fallback of OptimizeStackSize)
  *   developer builds only  "trace_variant" (s_memtime-instrumented / probe instantiations: 107, 113, 116, 213, 901-904, 961, 962), "graph_probe"   (libidkpt_dev.so, -DIDKPT_DEVELOPER) */
 IDKPT_API int32_t idkptSetDeveloperOption(idkpt_ctx* ctx, const char* name, int32_t value);

@@ -140,6 +140,16 @@ def test_refit_matches_oracle_refit(native_builder, oracle_builder):
     b = oracle_builder.refit(sc.blas_nodes, moved, sc.blas_triangles)
     assert a.tobytes() == b.tobytes()
     assert a.tobytes() != sc.blas_nodes.tobytes()
+    # +0 / -0 planted as box faces on every axis: everything on one side of zero is folded onto a zero of alternating sign.  Box.GrowToFit is minps / maxps (equal operands
+    # give the second), so faces hold zeros of both signs; a minimum that orders the zeros (-0 < +0) would not (the device refit: tests/test_gpu_adversarial_skeletons.py)
+    zeros = np.where(np.arange(moved.size).reshape(moved.shape) % 2 == 0, np.float32(0.0), np.float32(-0.0))
+    for side, field in ((1, "Min"), (-1, "Max")):
+        planted = np.where(moved * side < 0, zeros, moved).astype(np.float32)
+        a = native_builder.refit(sc.blas_nodes, planted, sc.blas_triangles)
+        b = oracle_builder.refit(sc.blas_nodes, planted, sc.blas_triangles)
+        assert a.tobytes() == b.tobytes()
+        face = b[field][1:]
+        assert (np.signbit(face) & (face == 0)).sum() > 100 and (~np.signbit(face) & (face == 0)).sum() > 100
 
 
 def test_tlas_structure(native_builder):

@@ -53,7 +53,7 @@ def test_struct_layout_matches_the_header(tmp_path):
     subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
     from idkengine_amd import gputypes as T
     got = [int(v) for v in subprocess.check_output([str(exe)]).decode().split()]
-    assert got == [C.sizeof(T.Denoise), T.Denoise.Iterations.offset, T.Denoise.ColorSigma.offset, T.Denoise.AlbedoSigma.offset, T.Denoise.NormalSigma.offset, T.Denoise.DemodulateAlbedo.offset, 12]
+    assert got == [C.sizeof(T.Denoise), T.Denoise.Iterations.offset, T.Denoise.ColorSigma.offset, T.Denoise.AlbedoSigma.offset, T.Denoise.NormalSigma.offset, T.Denoise.DemodulateAlbedo.offset, 13]
 
 
 # ---- the host build of the kernels' per-pixel function

@@ -53,7 +53,7 @@ def test_struct_layout_matches_the_header(tmp_path):
     subprocess.check_call(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(c), "-o", str(exe)])
     from idkengine_amd import gputypes as T
     got = [int(v) for v in subprocess.check_output([str(exe)]).decode().split()]
-    assert got == [C.sizeof(T.DenoiseVariance)] + [getattr(T.DenoiseVariance, f).offset for f in fields] + [12]
+    assert got == [C.sizeof(T.DenoiseVariance)] + [getattr(T.DenoiseVariance, f).offset for f in fields] + [13]
     assert got[:7] == [24, 0, 4, 8, 12, 16, 20]
 
 

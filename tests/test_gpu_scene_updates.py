@@ -10,6 +10,8 @@ sys.path.insert(0, HERE)
 import configs  # noqa: E402,F401
 from idkengine_amd import scenes as S  # noqa: E402,F401
 from gpu_helpers import bits, gpu_render, oracle_render, assert_equal  # noqa: E402,F401
+import skin_ref  # noqa: E402
+from skin_ref import _skin_numpy  # noqa: E402,F401  (tests/test_glref.py and tests/test_glref_full.py import it from here)
 
 pytestmark = pytest.mark.gpu
 
@@ -55,23 +57,15 @@ def test_refit_and_skinning_match_oracle(oracle_mod, oracle_builder, native_buil
     p = un["Position"].astype(f)
     want_pos = np.stack([(((M[:, i, 0] * p[:, 0] + M[:, i, 1] * p[:, 1]).astype(f) + M[:, i, 2] * p[:, 2]).astype(f) + M[:, i, 3] * f(1.0)).astype(f) for i in range(3)], 1)
     assert (bits(pos) == bits(want_pos)).all()
+    # normals, tangents and the previous positions: the restatement of the whole call (tests/skin_ref.py), word for word
+    nv = len(sc.vertices)
+    w_pos, w_prev, w_verts = skin_ref.skin(un, joints, moved, sc.vertices, 0, 0, 0, n)
+    verts = pt.DownloadBuffer(T.IDKPT_BUF_VERTICES, T.GpuVertex, nv)
+    assert (verts["Normal"] == w_verts["Normal"]).all() and (verts["Tangent"] == w_verts["Tangent"]).all() and verts.tobytes() == w_verts.tobytes()
+    assert (verts["Normal"][:n] != sc.vertices["Normal"][:n]).any()
+    assert pt.DownloadBuffer(T.IDKPT_BUF_PREV_VERTEX_POSITIONS, np.float32, 3 * nv).tobytes() == w_prev.tobytes() and w_prev[:n].tobytes() == moved[:n].tobytes()
+    assert pt.DownloadBuffer(1, np.float32, 3 * nv).tobytes() == w_pos.tobytes()
     pt.Dispose()
-
-
-def _skin_numpy(un, joints):
-    """Shaders/Skinning/compute.glsl:14-47 for the positions, binary32, operation for operation (weights * joint matrices summed in order)."""
-    f = np.float32
-    n = len(un)
-    M = np.zeros((n, 3, 4), f)
-    for r in range(3):
-        for k in range(4):
-            acc = None
-            for j in range(4):
-                term = un["JointWeights"][:, j].astype(f) * joints[un["JointIndices"][:, j], r, k].astype(f)
-                acc = term if acc is None else (acc + term).astype(f)
-            M[:, r, k] = acc
-    p = un["Position"].astype(f)
-    return np.stack([(((M[:, i, 0] * p[:, 0] + M[:, i, 1] * p[:, 1]).astype(f) + M[:, i, 2] * p[:, 2]).astype(f) + M[:, i, 3] * f(1.0)).astype(f) for i in range(3)], 1)
 
 
 @pytest.mark.parametrize("devices", [1, 2])
@@ -99,7 +93,8 @@ def test_animated_frames_skin_refit_tlas_render(oracle_mod, oracle_builder, nati
     un["Position"] = sc.vertex_positions[:nskin]; un["Normal"] = sc.vertices["Normal"][:nskin]; un["Tangent"] = sc.vertices["Tangent"][:nskin]
     un["JointIndices"] = rng.integers(0, 2, (nskin, 4)); wts = rng.uniform(0, 1, (nskin, 4)).astype(np.float32); un["JointWeights"] = wts / wts.sum(1, keepdims=True)
     pt.UploadUnskinnedVertices(un)
-    host = copy.copy(sc); host.vertex_positions = sc.vertex_positions.copy(); host.blas_nodes = sc.blas_nodes.copy(); host.mesh_transforms = sc.mesh_transforms.copy()
+    host = copy.copy(sc); host.vertex_positions = sc.vertex_positions.copy(); host.blas_nodes = sc.blas_nodes.copy(); host.mesh_transforms = sc.mesh_transforms.copy(); host.vertices = sc.vertices.copy()
+    prev = None
     o = None
     for frame in range(3):
         a = 0.25 * (frame + 1)
@@ -114,14 +109,19 @@ def test_animated_frames_skin_refit_tlas_render(oracle_mod, oracle_builder, nati
         pt.UpdateBuffer(T.IDKPT_BUF_MESH_TRANSFORMS, xf); pt.BuildTlasOnDevice()
         pt.ResetAccumulation(); pt.Compute()
         # ---- host equivalent for the oracle
-        host.vertex_positions[:nskin] = _skin_numpy(un, joints)
+        before = host.vertex_positions.copy()
+        host.vertex_positions, want_prev, host.vertices = skin_ref.skin(un, joints, host.vertex_positions, host.vertices, 0, 0, 0, nskin, prev_positions=prev)
+        prev = want_prev
+        assert host.vertex_positions[:nskin].tobytes() == _skin_numpy(un, joints).tobytes() and want_prev[:nskin].tobytes() == before[:nskin].tobytes()
         d0 = host.blas_descs[0]
         nodes0 = oracle_builder.refit(host.blas_nodes[d0["NodeOffset"]: d0["NodeOffset"] + d0["NodeCount"]], host.vertex_positions,
                                       host.blas_triangles[d0["TriangleOffset"]: d0["TriangleOffset"] + d0["TriangleCount"]])
         host.blas_nodes[d0["NodeOffset"]: d0["NodeOffset"] + d0["NodeCount"]] = nodes0
         host.mesh_transforms = xf
         S.rebuild_tlas(host, oracle_builder)
-        host.vertices = pt.DownloadBuffer(T.IDKPT_BUF_VERTICES, T.GpuVertex, len(sc.vertices))    # skinned + re-compressed normals / tangents (positions are checked against numpy below)
+        # skinned + re-compressed normals / tangents: the device's must BE the restatement's, and the oracle is fed the restatement's — nothing of its scene comes from the device
+        assert pt.DownloadBuffer(T.IDKPT_BUF_VERTICES, T.GpuVertex, len(sc.vertices)).tobytes() == host.vertices.tobytes(), frame
+        assert pt.DownloadBuffer(T.IDKPT_BUF_PREV_VERTEX_POSITIONS, np.float32, 3 * len(sc.vertices)).tobytes() == prev.tobytes(), frame
         assert pt.DownloadBuffer(T.IDKPT_BUF_VERTEX_POSITIONS, np.float32, 3 * nskin).tobytes() == host.vertex_positions[:nskin].tobytes(), frame
         assert pt.DownloadBuffer(T.IDKPT_BUF_BLAS_NODES, T.GpuBlasNode, len(host.blas_nodes)).tobytes() == host.blas_nodes.tobytes(), frame
         assert pt.DownloadBuffer(T.IDKPT_BUF_TLAS_NODES, T.GpuTlasNode, len(host.tlas_nodes)).tobytes() == host.tlas_nodes.tobytes(), frame
