@@ -22,6 +22,8 @@ SYMBOLS = [
     "idkptCollideSpheres", "idkptCollideSpheresDevice",
     "idkptDenoise", "idkptUploadDenoised", "idkptDownloadDenoised", "idkptGetDenoisedDevicePtr", "idkptGetDenoiseRoute", "idkptSetResultSource", "idkptGetResultSource", "idkptDenoiseVariance",
     "idkptSetNoiseEstimate", "idkptGetNoiseEstimate", "idkptEstimateNoise", "idkptDownloadNoise", "idkptGetNoiseDevicePtr", "idkptDownloadMoments", "idkptGetMomentsDevicePtr",
+    "idkptCaptureGeometry", "idkptDownloadGeometry", "idkptGetGeometryDevicePtr", "idkptReproject", "idkptDownloadTemporal", "idkptGetTemporalDevicePtr", "idkptUseTemporalAsDenoised",
+    "idkptSetDenoiseInput", "idkptGetDenoiseInput",
 ]
 
 _lib = None
@@ -56,6 +58,9 @@ def load():
         "idkptSetResultSource": [vp, i32], "idkptGetResultSource": [vp, C.POINTER(i32)], "idkptDenoiseVariance": [vp, i32, vp],
         "idkptSetNoiseEstimate": [vp, i32], "idkptGetNoiseEstimate": [vp, C.POINTER(i32)], "idkptEstimateNoise": [vp, i32, vp], "idkptDownloadNoise": [vp, i32, vp, sz, vp],
         "idkptGetNoiseDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(vp), C.POINTER(sz)], "idkptDownloadMoments": [vp, i32, vp, sz], "idkptGetMomentsDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(sz)],
+        "idkptCaptureGeometry": [vp, i32], "idkptDownloadGeometry": [vp, i32, vp, sz], "idkptGetGeometryDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(sz)], "idkptReproject": [vp, i32, i32, vp],
+        "idkptDownloadTemporal": [vp, i32, vp, sz], "idkptGetTemporalDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(sz)], "idkptUseTemporalAsDenoised": [vp, i32],
+        "idkptSetDenoiseInput": [vp, i32], "idkptGetDenoiseInput": [vp, C.POINTER(i32)],
         "idkptRefitBlas": [vp, i32], "idkptUploadUnskinnedVertices": [vp, vp, i32], "idkptSkin": [vp, u32, u32, u32, u32],
         "idkptDownloadBuffer": [vp, i32, sz, sz, vp], "idkptResetAccumulation": [vp], "idkptSetSampleSequence": [vp, u32, u32], "idkptGetAccumulatedSamples": [vp, C.POINTER(u32)],
         "idkptRender": [vp], "idkptSynchronize": [vp], "idkptDownload": [vp, i32, vp, sz], "idkptDownloadRays": [vp, vp, sz],

@@ -59,7 +59,8 @@ struct PinnedUpload {
 
 // ---- frame products -----------------------------------------------------------------------------------------------------------------------------------
 // What is made of a finished frame on request: the display image (idkptPresent, host_readback.hpp), the bloom chains (idkptBloom, host_bloom.hpp), the denoised image
-// (idkptDenoise / idkptUploadDenoised, host_denoise.hpp), the noise estimate and the moments images it reads (idkptEstimateNoise, host_noise.hpp).  Their life cycle is
+// (idkptDenoise / idkptUploadDenoised, host_denoise.hpp), the noise estimate and the moments images it reads (idkptEstimateNoise, host_noise.hpp), the geometry and temporal
+// images (idkptCaptureGeometry / idkptReproject, host_reproject.hpp).  Their life cycle is
 // stated HERE and nowhere else: the buffers belong to a ring slot and a frame size; they are made at the slot's first use (a context that never asks pays nothing), every
 // buffer ends in GUARD_BYTES of 0xA5 that no kernel writes (include/idkpt.h: what a host or a test looks at to see that nothing ran past the payload); every resize releases
 // them (alloc_frame_impl -> release_all), idkptSetPresentationSize releases those that have the presentation size, idkptSetMaxBatch keeps them (alloc_frame_keep_images moves
@@ -110,16 +111,23 @@ struct NoiseSlot {
     void release() { tiles.release(); summary.release(); valid = false; }
 };
 
+// idkptCaptureGeometry / idkptReproject: the geometry image (world position or miss direction, id bits) and the temporal image (rgb, effective sample count), both RGBA32F
+struct TemporalSlot {
+    GuardedBuf geom, temporal;
+    bool geomValid = false, temporalValid = false;                           // captured / reprojected since the last resize
+    void release() { geom.release(); temporal.release(); geomValid = false; temporalValid = false; }
+};
+
 static bool slot_holds(const DisplaySlot& s) { return s.format >= 0; }
 template <class S> static bool slot_holds(const S& s) { return s.valid; }
 
 struct FrameProducts {
-    std::vector<DisplaySlot> display; std::vector<BloomSlot> bloom; std::vector<DenoiseSlot> denoise; std::vector<NoiseSlot> noise;
+    std::vector<DisplaySlot> display; std::vector<BloomSlot> bloom; std::vector<DenoiseSlot> denoise; std::vector<NoiseSlot> noise; std::vector<TemporalSlot> temporal;
     DevBuf moments;              // idkptSetNoiseEstimate: the moments images (m1, m2, 0, 1) of ALL ring slots in one allocation, each followed by its guard (host_noise.hpp noise_moments_ensure)
     template <class S> static void drop(std::vector<S>& v) { for (S& s : v) s.release(); v.clear(); }
     void release_noise() { drop(noise); moments.release(); }
     void release_presentation_sized() { drop(display); drop(bloom); }
-    void release_all() { release_presentation_sized(); drop(denoise); release_noise(); }
+    void release_all() { release_presentation_sized(); drop(denoise); release_noise(); drop(temporal); }
     // the record of a ring slot that is about to be made: the vector gets the ring's size at its first use after a release
     template <class S> static S& slot(std::vector<S>& v, int ringSize, int slot) { if (v.size() != (size_t)ringSize) { drop(v); v.resize(ringSize); } return v[slot]; }
 };
@@ -279,6 +287,8 @@ struct dev_ctx {
     int presW = 0, presH = 0;       // idkptSetPresentationSize: the size of the display and bloom images (0, 0: the render size); a state of its own, kept by every resize
     int resultSource = 0;           // idkptSetResultSource (enum idkpt_result_source): what IDKPT_IMAGE_RESULT means to idkptPresent and idkptBloom; a state of its own, kept by every resize
     PinnedUpload denoiseStage;      // idkptUploadDenoised's host image
+    int denoiseInput = 0;           // idkptSetDenoiseInput (enum idkpt_denoise_input): where idkptDenoise takes its colour from; a state of its own, kept by every resize
+    DevBuf geomRays, geomHits;      // idkptCaptureGeometry: the centre rays of one frame and their hits (W * rows of each), kept between calls
     int noiseOn = 0;                // idkptSetNoiseEstimate: FinalDraw folds every sample's luminance into the moments images as well; a state of its own, kept by every resize
     DevBuf camTab;                                       // per-sample cameras of the batch being launched (ring mode)
     int rowLimit = 0x7fffffff;                           // idkptSetRowRange: at most this many local rows

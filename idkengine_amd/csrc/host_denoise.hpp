@@ -24,6 +24,9 @@ static int32_t dev_Denoise(dev_ctx* ctx, int32_t slot, const idkpt_denoise* d)
     { int rc = denoise_scope(ctx, "idkptDenoise"); if (rc) return rc; }
     if (!ctx->st.OutputAOVs) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptDenoise: the current settings have OutputAOVs = 0: the albedo and normal images that guide the filter are not accumulated");
     if (slot < 0) slot = ctx->curSlot;
+    const bool temporalIn = ctx->denoiseInput == IDKPT_DENOISE_INPUT_TEMPORAL;   // idkptSetDenoiseInput: c0 is the slot's temporal rgb (host_reproject.hpp)
+    if (temporalIn && !((size_t)slot < ctx->products.temporal.size() && ctx->products.temporal[slot].temporalValid))
+        return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptDenoise: the denoise input is IDKPT_DENOISE_INPUT_TEMPORAL and the slot holds no temporal image since the last resize (idkptReproject)");
     HIPC(hipSetDevice(ctx->device));
     FLUSH_KEEP();                                        // stream-ordered behind what was queued (as idkptBloom)
     { int rc = check_overflow(ctx); if (rc) return rc; }   // (no wait: see idkptGetFrameDevicePtr)
@@ -35,7 +38,7 @@ static int32_t dev_Denoise(dev_ctx* ctx, int32_t slot, const idkpt_denoise* d)
     for (int k = 0; k < 2 && k < n - 1; k++) HIPC(s.ping[k].ensure(ctx->stream, bytes));
     const float4* albedo = image_ptr(ctx, IDKPT_IMAGE_ALBEDO, slot); const float4* normal = image_ptr(ctx, IDKPT_IMAGE_NORMAL, slot);
     const dim3 grid((unsigned)((W + denoisek::TILE - 1) / denoisek::TILE), (unsigned)((H + denoisek::TILE - 1) / denoisek::TILE));
-    const float4* src = image_ptr(ctx, IDKPT_IMAGE_RESULT, slot);
+    const float4* src = temporalIn ? ctx->products.temporal[slot].temporal.as<const float4>() : image_ptr(ctx, IDKPT_IMAGE_RESULT, slot);
     for (int i = 0; i < n; i++) {
         float4* dst = (i == n - 1 ? s.out : s.ping[i & 1]).as<float4>();
         denoisek::Params p;

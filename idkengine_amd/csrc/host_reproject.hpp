@@ -1,0 +1,141 @@
+// host_reproject.hpp — idkptCaptureGeometry / idkptDownloadGeometry / idkptGetGeometryDevicePtr / idkptReproject / idkptDownloadTemporal / idkptGetTemporalDevicePtr /
+// idkptUseTemporalAsDenoised / idkptSetDenoiseInput: the geometry image and the temporal image of a ring slot (kernels: kernels_reproject.hpp; the contract: include/idkpt.h,
+// "temporal reprojection").  Part of the single translation unit idkpt.hip (included there, behind host_queries.hpp, whose closest-hit core traces the centre rays, and
+// host_denoise.hpp, whose scope check and slot record it uses).
+// Queued samples are launched first, nothing but the downloads waits for the GPU.  Frame products (host_context.hpp, "frame products": the life cycle of the buffers): a
+// TemporalSlot per ring slot, both images RGBA32F of the render size; the ray and hit scratch of a capture belongs to the context and is sized for one frame.
+// One device, the whole frame (the scope of idkptDenoise): a pixel's history may lie in any row.
+#pragma once
+
+static int32_t dev_CaptureGeometry(dev_ctx* ctx, int32_t slot)
+{
+    if (!ctx) return IDKPT_ERR_INVALID_ARGUMENT;
+    REQUIRE(slot >= -1 && slot < ctx->ringSize, "idkptCaptureGeometry: slot outside the frame ring (-1: the current slot)");
+    { int rc = denoise_scope(ctx, "idkptCaptureGeometry"); if (rc) return rc; }
+    if (!ctx->haveScene) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptCaptureGeometry: no scene uploaded");
+    if (slot < 0) slot = ctx->curSlot;
+    HIPC(hipSetDevice(ctx->device));
+    FLUSH_KEEP();                                        // stream-ordered behind what was queued (as idkptDenoise); the accumulation is not touched
+    const int W = ctx->W, H = ctx->H;
+    const size_t N = (size_t)W * ctx->rows;
+    REQUIRE(N < (1ull << 31), "idkptCaptureGeometry: too many pixels for one ray query");
+    HIPC(ctx->geomRays.ensure(N * sizeof(idkpt_ray))); HIPC(ctx->geomHits.ensure(N * sizeof(idkpt_hit)));
+    TemporalSlot& s = FrameProducts::slot(ctx->products.temporal, ctx->ringSize, slot);
+    HIPC(s.geom.ensure(ctx->stream, N * 16));
+    reprojk::Camera cam;
+    memcpy(cam.invProj, ctx->invProj, sizeof(cam.invProj)); memcpy(cam.invView, ctx->invView, sizeof(cam.invView));   // the camera current at the call
+    const dim3 grid((unsigned)((N + 255) / 256));
+    hipLaunchKernelGGL(k_geom_rays, grid, dim3(256), 0, ctx->stream, cam, W, H, (uint32_t)N, ctx->geomRays.as<idkpt_ray>());
+    HIPC(hipGetLastError());
+    { int rc = dev_TraceRaysDevice(ctx, ctx->geomRays.as<idkpt_ray>(), N, 0u, ctx->geomHits.as<idkpt_hit>()); if (rc) return rc; }   // closest hit, no lights: the core idkptTraceRaysDevice is held to the oracle with
+    s.geomValid = false;                                 // (a refused trace launched nothing: the previous record stays)
+    hipLaunchKernelGGL(k_geom_pack, grid, dim3(256), 0, ctx->stream, (const idkpt_ray*)ctx->geomRays.as<idkpt_ray>(), (const idkpt_hit*)ctx->geomHits.as<idkpt_hit>(), (uint32_t)N, s.geom.as<float4>());
+    HIPC(hipGetLastError());
+    s.geomValid = true;
+    return IDKPT_OK;
+}
+
+// the record of ring slot `slot` (-1: the current one) for the calls that read one of its two images
+static int32_t temporal_slot_of(dev_ctx* ctx, const char* who, int32_t slot, bool geometry, TemporalSlot** out)
+{
+    REQUIRE(slot >= -1 && slot < ctx->ringSize, std::string(who) + ": slot outside the frame ring (-1: the current slot)");
+    if (slot < 0) slot = ctx->curSlot;
+    std::vector<TemporalSlot>& v = ctx->products.temporal;
+    if ((size_t)slot >= v.size() || !(geometry ? v[slot].geomValid : v[slot].temporalValid))
+        return fail(ctx, IDKPT_ERR_INVALID_OPERATION, std::string(who) + (geometry ? ": the slot holds no geometry image since the last resize (idkptCaptureGeometry)" : ": the slot holds no temporal image since the last resize (idkptReproject)"));
+    *out = &v[slot];
+    return IDKPT_OK;
+}
+static int32_t temporal_download(dev_ctx* ctx, const char* who, int32_t slot, bool geometry, float* rgba, size_t bytes)
+{
+    if (!ctx || !rgba) return IDKPT_ERR_INVALID_ARGUMENT;
+    TemporalSlot* s = nullptr;
+    { int rc = temporal_slot_of(ctx, who, slot, geometry, &s); if (rc) return rc; }
+    const GuardedBuf& b = geometry ? s->geom : s->temporal;
+    REQUIRE(bytes == b.bytes, std::string(who) + ": bytes must equal height*width*16");
+    return download_behind_queue(ctx, rgba, b.mem.p, bytes);
+}
+static int32_t temporal_device_ptr(dev_ctx* ctx, const char* who, int32_t slot, bool geometry, void** outPtr, size_t* outBytes)
+{
+    if (!ctx || !outPtr) return IDKPT_ERR_INVALID_ARGUMENT;
+    TemporalSlot* s = nullptr;
+    { int rc = temporal_slot_of(ctx, who, slot, geometry, &s); if (rc) return rc; }
+    const GuardedBuf& b = geometry ? s->geom : s->temporal;
+    *outPtr = b.mem.p;
+    if (outBytes) *outBytes = b.bytes;
+    return IDKPT_OK;
+}
+static int32_t dev_DownloadGeometry(dev_ctx* ctx, int32_t slot, float* rgba, size_t bytes) { return temporal_download(ctx, "idkptDownloadGeometry", slot, true, rgba, bytes); }
+static int32_t dev_GetGeometryDevicePtr(dev_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes) { return temporal_device_ptr(ctx, "idkptGetGeometryDevicePtr", slot, true, outPtr, outBytes); }
+static int32_t dev_DownloadTemporal(dev_ctx* ctx, int32_t slot, float* rgba, size_t bytes) { return temporal_download(ctx, "idkptDownloadTemporal", slot, false, rgba, bytes); }
+static int32_t dev_GetTemporalDevicePtr(dev_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes) { return temporal_device_ptr(ctx, "idkptGetTemporalDevicePtr", slot, false, outPtr, outBytes); }
+
+static int32_t dev_Reproject(dev_ctx* ctx, int32_t slot, int32_t historySlot, const idkpt_reproject* r)
+{
+    if (!ctx || !r) return IDKPT_ERR_INVALID_ARGUMENT;
+    REQUIRE(slot >= -1 && slot < ctx->ringSize, "idkptReproject: slot outside the frame ring (-1: the current slot)");
+    REQUIRE(historySlot == IDKPT_NO_HISTORY || (historySlot >= 0 && historySlot < ctx->ringSize), "idkptReproject: historySlot must be IDKPT_NO_HISTORY or a slot of the frame ring");
+    REQUIRE(reprojt::finite(r->PositionTolerance) && r->PositionTolerance > 0.0f, "idkptReproject: PositionTolerance must be finite and > 0");
+    REQUIRE(reprojt::finite(r->MaxHistory) && r->MaxHistory >= 1.0f, "idkptReproject: MaxHistory must be finite and >= 1");
+    if (slot < 0) slot = ctx->curSlot;
+    REQUIRE(slot != historySlot, "idkptReproject: slot and historySlot must differ (a frame is no history of itself)");
+    { int rc = denoise_scope(ctx, "idkptReproject"); if (rc) return rc; }
+    std::vector<TemporalSlot>& v = ctx->products.temporal;
+    auto holds = [&](int q, bool geometry) { return (size_t)q < v.size() && (geometry ? v[q].geomValid : v[q].temporalValid); };
+    if (!holds(slot, true)) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptReproject: the slot holds no geometry image since the last resize (idkptCaptureGeometry)");
+    const bool start = historySlot == IDKPT_NO_HISTORY;
+    if (!start && !holds(historySlot, true)) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptReproject: the history slot holds no geometry image since the last resize (idkptCaptureGeometry)");
+    if (!start && !holds(historySlot, false)) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptReproject: the history slot holds no temporal image since the last resize (idkptReproject)");
+    const uint32_t n = ctx->accum[slot];                 // (queued samples included: they are launched below)
+    if (n == 0u) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptReproject: the slot has accumulated no sample");
+    HIPC(hipSetDevice(ctx->device));
+    FLUSH_KEEP();                                        // stream-ordered behind what was queued (as idkptDenoise)
+    { int rc = check_overflow(ctx); if (rc) return rc; }   // (no wait: see idkptGetFrameDevicePtr)
+    const int W = ctx->W, H = ctx->H;
+    TemporalSlot& s = v[slot];
+    s.temporalValid = false;
+    HIPC(s.temporal.ensure(ctx->stream, (size_t)W * H * 16));
+    reprojt::Params p;
+    p.W = W; p.H = H;
+    memcpy(p.M, r->PrevProjView, sizeof(p.M)); memcpy(p.prevPos, r->PrevViewPos, sizeof(p.prevPos));
+    p.tol2 = r->PositionTolerance * r->PositionTolerance; p.maxHistory = r->MaxHistory; p.n = (float)n;
+    const dim3 grid((unsigned)((W + reprojk::TILE - 1) / reprojk::TILE), (unsigned)((H + reprojk::TILE - 1) / reprojk::TILE));
+    const float4* hg = start ? nullptr : v[historySlot].geom.as<const float4>();
+    const float4* hc = start ? nullptr : v[historySlot].temporal.as<const float4>();
+    hipLaunchKernelGGL(k_reproject, grid, dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, IDKPT_IMAGE_RESULT, slot), s.geom.as<const float4>(), hg, hc, s.temporal.as<float4>(), p);
+    HIPC(hipGetLastError());
+    s.temporalValid = true;
+    return IDKPT_OK;
+}
+
+// the device-side sibling of idkptUploadDenoised: the slot's temporal rgb, alpha 1.0, becomes its denoised image
+static int32_t dev_UseTemporalAsDenoised(dev_ctx* ctx, int32_t slot)
+{
+    if (!ctx) return IDKPT_ERR_INVALID_ARGUMENT;
+    REQUIRE(slot >= -1 && slot < ctx->ringSize, "idkptUseTemporalAsDenoised: slot outside the frame ring (-1: the current slot)");
+    { int rc = denoise_scope(ctx, "idkptUseTemporalAsDenoised"); if (rc) return rc; }
+    TemporalSlot* t = nullptr;
+    { int rc = temporal_slot_of(ctx, "idkptUseTemporalAsDenoised", slot, false, &t); if (rc) return rc; }
+    if (slot < 0) slot = ctx->curSlot;
+    HIPC(hipSetDevice(ctx->device));
+    FLUSH_KEEP();
+    const size_t N = (size_t)ctx->W * ctx->H;
+    DenoiseSlot& s = FrameProducts::slot(ctx->products.denoise, ctx->ringSize, slot);
+    s.valid = false; s.iterations = 0;
+    HIPC(s.out.ensure(ctx->stream, N * 16));
+    hipLaunchKernelGGL(k_temporal_to_denoised, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, t->temporal.as<const float4>(), (uint32_t)N, s.out.as<float4>());
+    HIPC(hipGetLastError());
+    s.valid = true;
+    return IDKPT_OK;
+}
+
+static int32_t dev_SetDenoiseInput(dev_ctx* ctx, int32_t input)
+{
+    if (!ctx) return IDKPT_ERR_INVALID_ARGUMENT;
+    REQUIRE(input == IDKPT_DENOISE_INPUT_ACCUMULATED || input == IDKPT_DENOISE_INPUT_TEMPORAL, "idkptSetDenoiseInput: input must be IDKPT_DENOISE_INPUT_ACCUMULATED or IDKPT_DENOISE_INPUT_TEMPORAL");
+    if (input == IDKPT_DENOISE_INPUT_TEMPORAL && !owns_whole_frame(ctx))
+        return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptSetDenoiseInput: the temporal image needs the whole frame on one device; this context holds a shard of the rows or is a member of a multi-device context");
+    ctx->denoiseInput = input;
+    return IDKPT_OK;
+}
+static int32_t dev_GetDenoiseInput(dev_ctx* ctx, int32_t* out) { if (!ctx || !out) return IDKPT_ERR_INVALID_ARGUMENT; *out = ctx->denoiseInput; return IDKPT_OK; }

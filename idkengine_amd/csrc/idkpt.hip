@@ -39,6 +39,7 @@ using namespace ptd;
 #include "kernels_denoise.hpp"
 #include "kernels_noise.hpp"
 #include "kernels_denoise_variance.hpp"
+#include "kernels_reproject.hpp"
 #include "kernels_present.hpp"
 #include "bvh_gpu.hpp"
 #include "bvh_gpu_full.hpp"
@@ -58,6 +59,7 @@ using namespace ptd;
 #include "host_bloom.hpp"
 #include "host_denoise.hpp"
 #include "host_denoise_variance.hpp"
+#include "host_reproject.hpp"
 #include "host_options.hpp"
 #include "transport_rccl.hpp"
 

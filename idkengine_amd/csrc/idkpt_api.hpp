@@ -936,6 +936,26 @@ int32_t idkptGetNoiseDevicePtr(idkpt_ctx* c, int32_t slot, void** outTiles, void
 int32_t idkptDownloadMoments(idkpt_ctx* c, int32_t slot, float* rgba, size_t bytes) { ONE_ONLY("idkptDownloadMoments", NOISE_WHY, dev_DownloadMoments(m, slot, rgba, bytes)); }
 int32_t idkptGetMomentsDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size_t* outBytes) { ONE_ONLY("idkptGetMomentsDevicePtr", NOISE_WHY, dev_GetMomentsDevicePtr(m, slot, outPtr, outBytes)); }
 
+// ---- temporal reprojection (host_reproject.hpp): one device, the whole frame — a pixel's history may lie in any row of the history frame
+#define REPROJECT_WHY ": temporal reprojection needs the whole frame on one device"
+int32_t idkptCaptureGeometry(idkpt_ctx* c, int32_t slot) { ONE_ONLY("idkptCaptureGeometry", REPROJECT_WHY, dev_CaptureGeometry(m, slot)); }
+int32_t idkptDownloadGeometry(idkpt_ctx* c, int32_t slot, float* rgba, size_t bytes) { ONE_ONLY("idkptDownloadGeometry", REPROJECT_WHY, dev_DownloadGeometry(m, slot, rgba, bytes)); }
+int32_t idkptGetGeometryDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size_t* outBytes) { ONE_ONLY("idkptGetGeometryDevicePtr", REPROJECT_WHY, dev_GetGeometryDevicePtr(m, slot, outPtr, outBytes)); }
+int32_t idkptReproject(idkpt_ctx* c, int32_t slot, int32_t historySlot, const idkpt_reproject* reproject) { ONE_ONLY("idkptReproject", REPROJECT_WHY, dev_Reproject(m, slot, historySlot, reproject)); }
+int32_t idkptDownloadTemporal(idkpt_ctx* c, int32_t slot, float* rgba, size_t bytes) { ONE_ONLY("idkptDownloadTemporal", REPROJECT_WHY, dev_DownloadTemporal(m, slot, rgba, bytes)); }
+int32_t idkptGetTemporalDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size_t* outBytes) { ONE_ONLY("idkptGetTemporalDevicePtr", REPROJECT_WHY, dev_GetTemporalDevicePtr(m, slot, outPtr, outBytes)); }
+int32_t idkptUseTemporalAsDenoised(idkpt_ctx* c, int32_t slot) { ONE_ONLY("idkptUseTemporalAsDenoised", REPROJECT_WHY, dev_UseTemporalAsDenoised(m, slot)); }
+// the denoise input: a multi-device context stays at IDKPT_DENOISE_INPUT_ACCUMULATED (it has no temporal image)
+int32_t idkptSetDenoiseInput(idkpt_ctx* c, int32_t input)
+{
+    if (!c) return IDKPT_ERR_INVALID_ARGUMENT;
+    ONE(dev_SetDenoiseInput(m, input));
+    GREQ(input == IDKPT_DENOISE_INPUT_ACCUMULATED || input == IDKPT_DENOISE_INPUT_TEMPORAL, "idkptSetDenoiseInput: input must be IDKPT_DENOISE_INPUT_ACCUMULATED or IDKPT_DENOISE_INPUT_TEMPORAL");
+    if (input == IDKPT_DENOISE_INPUT_TEMPORAL) return gfail(c, IDKPT_ERR_INVALID_OPERATION, "idkptSetDenoiseInput: the temporal image needs the whole frame on one device; a multi-device context has none");
+    return IDKPT_OK;
+}
+int32_t idkptGetDenoiseInput(idkpt_ctx* c, int32_t* outInput) { if (!c || !outInput) return IDKPT_ERR_INVALID_ARGUMENT; return dev_GetDenoiseInput(c->dev[0], outInput); }
+
 int32_t idkptResetAccumulation(idkpt_ctx* c) { if (!c) return IDKPT_ERR_INVALID_ARGUMENT; for (dev_ctx* m : c->dev) dev_ResetAccumulation(m); return IDKPT_OK; }
 int32_t idkptSetSampleSequence(idkpt_ctx* c, uint32_t first, uint32_t stride) { REPLICATE(SetSampleSequence, first, stride); }
 int32_t idkptGetAccumulatedSamples(idkpt_ctx* c, uint32_t* out) { if (!c || !out) return IDKPT_ERR_INVALID_ARGUMENT; return dev_GetAccumulatedSamples(c->dev[0], out); }

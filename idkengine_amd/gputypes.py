@@ -223,6 +223,26 @@ class NoiseSummary(C.Structure):
     _fields_ = [("TilesAbove", C.c_uint32), ("MaxTileMean", C.c_float), ("Tiles", C.c_uint32), ("Samples", C.c_uint32)]
 
 
+IDKPT_NO_HISTORY = -2                                                   # idkptReproject's historySlot: start a history
+IDKPT_DENOISE_INPUT_ACCUMULATED, IDKPT_DENOISE_INPUT_TEMPORAL = 0, 1    # enum idkpt_denoise_input (idkptSetDenoiseInput): where idkptDenoise takes its colour from
+
+
+class Reproject(C.Structure):
+    """idkpt_reproject: the settings of idkptReproject (include/idkpt.h, "temporal reprojection"; no counterpart in the reference).  PrevProjView / PrevViewPos: the
+    ProjView matrix (View * Projection, OpenTK memory order) and the position of the camera the history slot's geometry was captured with.  The PositionTolerance and
+    MaxHistory defaults are starting values (profiles/reproject.md)."""
+    _fields_ = [("PrevProjView", C.c_float * 16), ("PrevViewPos", C.c_float * 3), ("PositionTolerance", C.c_float), ("MaxHistory", C.c_float)]
+
+    def __init__(self, PrevProjView=None, PrevViewPos=(0.0, 0.0, 0.0), PositionTolerance=0.02, MaxHistory=32.0):
+        m = np.eye(4, dtype=np.float32) if PrevProjView is None else np.asarray(PrevProjView, np.float32)
+        super().__init__((C.c_float * 16)(*m.reshape(16).tolist()), (C.c_float * 3)(*[float(v) for v in PrevViewPos]), float(PositionTolerance), float(MaxHistory))
+
+    @classmethod
+    def from_camera(cls, cam, **kw):
+        """the settings for a history frame rendered with scenes.Camera `cam`"""
+        return cls((cam.view @ cam.proj).astype(np.float32), cam.position, **kw)
+
+
 class Stats(C.Structure):
     _fields_ = [("RaysTraced", C.c_uint64), ("PrimaryRays", C.c_uint64), ("Frames", C.c_uint64),
                 ("LastAliveCounts", C.c_uint32 * 16), ("LastTraceMs", C.c_float), ("LastFrameMs", C.c_float),

@@ -697,6 +697,58 @@ class PathTracer:
         self._check(self._L.idkptGetMomentsDevicePtr(self._ctx, -1 if slot is None else int(slot), C.byref(p), C.byref(n)))
         return p.value, n.value
 
+    # ---- temporal reprojection (idkptCaptureGeometry / idkptReproject / idkptUseTemporalAsDenoised / idkptSetDenoiseInput): no counterpart in the reference
+    def CaptureGeometry(self, slot=None):
+        """idkptCaptureGeometry: one centre ray per pixel under the current camera -> the geometry image of ring slot `slot` (None: the current one)"""
+        self._check(self._L.idkptCaptureGeometry(self._ctx, -1 if slot is None else int(slot)))
+
+    def DownloadGeometry(self, slot=None):
+        """idkptDownloadGeometry: (H, W, 4) float32 — the world position of the pixel centre's hit and the bits of its MeshTransformId, or the ray direction and 0xFFFFFFFF"""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.idkptDownloadGeometry(self._ctx, -1 if slot is None else int(slot), out.ctypes.data, out.nbytes))
+        return out
+
+    def Reproject(self, slot=None, history=T.IDKPT_NO_HISTORY, settings=None):
+        """idkptReproject: blends Result of `slot` with the temporal image of ring slot `history` found through that frame's camera (settings: a gputypes.Reproject holding
+        its PrevProjView and PrevViewPos); history = IDKPT_NO_HISTORY starts a history.  Both slots need CaptureGeometry first.  The result stays in the slot's temporal
+        image (DownloadTemporal)."""
+        if settings is None:
+            settings = T.Reproject()
+        if not isinstance(settings, T.Reproject):
+            raise TypeError("Reproject: settings must be a gputypes.Reproject")
+        self._check(self._L.idkptReproject(self._ctx, -1 if slot is None else int(slot), int(history), C.addressof(settings)))
+
+    def DownloadTemporal(self, slot=None):
+        """idkptDownloadTemporal: (H, W, 4) float32 — rgb and the effective sample count"""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.idkptDownloadTemporal(self._ctx, -1 if slot is None else int(slot), out.ctypes.data, out.nbytes))
+        return out
+
+    def geometry_device_ptr(self, slot=None):
+        """idkptGetGeometryDevicePtr: (device pointer, bytes), valid in stream order; 64 guard bytes follow"""
+        p = C.c_void_p(); n = C.c_size_t()
+        self._check(self._L.idkptGetGeometryDevicePtr(self._ctx, -1 if slot is None else int(slot), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def temporal_device_ptr(self, slot=None):
+        """idkptGetTemporalDevicePtr: (device pointer, bytes), valid in stream order; 64 guard bytes follow"""
+        p = C.c_void_p(); n = C.c_size_t()
+        self._check(self._L.idkptGetTemporalDevicePtr(self._ctx, -1 if slot is None else int(slot), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def UseTemporalAsDenoised(self, slot=None):
+        """idkptUseTemporalAsDenoised: the slot's temporal rgb (alpha 1.0) becomes its denoised image; Present and Bloom show it under IDKPT_RESULT_DENOISED"""
+        self._check(self._L.idkptUseTemporalAsDenoised(self._ctx, -1 if slot is None else int(slot)))
+
+    def SetDenoiseInput(self, source):
+        """idkptSetDenoiseInput: gputypes.IDKPT_DENOISE_INPUT_ACCUMULATED (default) or IDKPT_DENOISE_INPUT_TEMPORAL — where Denoise takes its colour from"""
+        self._check(self._L.idkptSetDenoiseInput(self._ctx, int(source)))
+
+    def GetDenoiseInput(self):
+        s = C.c_int32()
+        self._check(self._L.idkptGetDenoiseInput(self._ctx, C.byref(s)))
+        return s.value
+
     def enable_counters(self, on=True):
         self._check(self._L.idkptEnableCounters(self._ctx, 1 if on else 0))
 

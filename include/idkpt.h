@@ -819,6 +819,89 @@ typedef struct idkpt_denoise_variance {
 } idkpt_denoise_variance;
 IDKPT_API int32_t idkptDenoiseVariance(idkpt_ctx* ctx, int32_t slot, const idkpt_denoise_variance* settings);   /* Result, Albedo, Normal and the moments of the slot -> its denoised image */
 
+/* ---- temporal reprojection (added under ABI 12; detect by symbol): carry the accumulated frame across camera moves -----------------------------------------------------
+ * THIS HAS NO COUNTERPART IN THE REFERENCE.  The engine resets the accumulation whenever the camera moves and waits for the picture to converge again; a host of this
+ * library that calls idkptResetAccumulation is back at one sample per pixel, the state every filter above handles worst (idkptDenoiseVariance refuses it).  The calls of
+ * this section are the other half of SVGF (Schied et al. 2017): a frame's pixels are looked up in the PREVIOUS frame's accumulated picture through the previous frame's
+ * camera and blended with it where the same surface is found there.  Three pieces: a geometry image per ring slot, the reprojection itself, and two ways for the
+ * existing consumers to read its result.  Everything is default-off and additive: a host that calls none of it runs what it ran before, bit for bit.
+ * Every operation of the texts below is a correctly rounded binary32 + - * / or floorf in the written order (-ffp-contract=off), sums run in the order written, so the
+ * texts define the results BIT FOR BIT; they are checked against an independent numpy restatement (tests/reproject_ref.py).
+ *
+ * The geometry image.  idkptCaptureGeometry(ctx, slot) fills one RGBA32F record per pixel of the slot (slot -1: the current slot) with what the pixel's CENTRE sees under
+ * the camera current at the call (idkptSetPerFrame / idkptSetPerFrameData): one ray per pixel, no jitter, no lens;
+ *     o = (InvView[12], InvView[13], InvView[14])          (the InvView translation, as the first-hit stage uses it)
+ *     d = GetWorldSpaceDirection(InvProjection, InvView, nx, ny), nx = ((float)x + 0.5f) / (float)width * 2 - 1, ny likewise with y and height   (the first-hit stage's
+ *         expression before its jitter; Shaders/include/Math.glsl)
+ *     traced as idkptTraceRaysDevice traces { o, FLT_MAX, d } with flags 0 (closest hit, no lights): the same core, the same hits.
+ *     hit:   record = (o.x + d.x * T, o.y + d.y * T, o.z + d.z * T, asfloat(MeshTransformId))
+ *     miss:  record = (d.x, d.y, d.z, asfloat(0xFFFFFFFF))
+ * Queued samples are launched first; the call is stream-ordered, waits for nothing, touches neither the accumulated images nor the accumulation, and sees every geometry
+ * update issued before it (as idkptCollideSpheres does).  It needs an uploaded scene.  idkptDownloadGeometry (bytes = height * width * 16; synchronises like the other
+ * Download calls) and idkptGetGeometryDevicePtr (stream-ordered, does not wait) read the record of a slot.
+ *
+ * The reprojection.  idkptReproject(ctx, slot, historySlot, r) writes the TEMPORAL image of `slot` (RGBA32F: rgb, and in alpha the effective sample count of the pixel).
+ * Inputs: cur = Result of `slot` as accumulated and n = (float) of its sample count (>= 1; queued samples are launched first); g = the geometry image of `slot`;
+ * hg = the geometry image and hc = the temporal image of `historySlot`; M = r->PrevProjView — the ProjView (View * Projection, OpenTK memory order, the order of
+ * idkptSetPerFrame's matrices) of the camera the history slot's geometry was captured with — and r->PrevViewPos, that camera's position.
+ * historySlot == IDKPT_NO_HISTORY starts a history: out = (cur.rgb, n) at every pixel.  Otherwise, per pixel, with p = g.xyz and id = the bits of g.w:
+ *   Clip coordinates.  clip_j = ((p.x * M[j] + p.y * M[4 + j]) + p.z * M[8 + j]) + M[12 + j] for j = 0 (x), 1 (y), 3 (w); for a miss (id == 0xFFFFFFFF: p is a direction,
+ *     w = 0) the last term is dropped.  If !(clip.w > 0): no history.
+ *   Previous pixel position.  u = (clip.x / clip.w * 0.5f + 0.5f) * (float)width - 0.5f, v likewise with clip.y and height.  If !(u > -1 && u < width && v > -1 &&
+ *     v < height): no history.  A NaN lands here; no value feeds an address unchecked.
+ *   Taps.  x0 = floorf(u), fx = u - x0, y0 = floorf(v), fy = v - y0.  The taps are (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1) in this order, their weights
+ *     (1 - fx) * (1 - fy), fx * (1 - fy), (1 - fx) * fy, fx * fy.
+ *   A tap q is VALID iff it lies inside the image; the id bits of hg_q equal id; for a hit, |p - hg_q.xyz|^2 <= (PositionTolerance * PositionTolerance) * |p - PrevViewPos|^2
+ *     with |a - b|^2 = (dx * dx + dy * dy) + dz * dz of the component differences a - b (the product of the tolerances is computed once per call); and all four channels
+ *     c of hc_q satisfy fabsf(c) <= FLT_MAX.
+ *   Blend.  Over the valid taps in order: sum += hc_q * w per channel (all four), sumW += w.  If sumW >= 0.01f:
+ *       h = sum / sumW per channel;  Hc = fminf(h.a, MaxHistory);
+ *       out.rgb = (h.rgb * Hc + cur.rgb * n) / (Hc + n);  out.a = Hc + n.
+ *     Otherwise, and wherever the text says "no history": out = (cur.rgb, n).
+ * So out is the mean of the history's (capped) samples and the frame's own, and its alpha says how many samples stand behind it; the next frame uses this slot as its
+ * history.  The cap bounds the lag behind changes of lighting: with MaxHistory = 32 a pixel forgets 1/33 of its past with every one-sample frame.
+ * WHAT DETECTS CHANGE.  The position test compares WORLD positions: a tap is rejected where a different surface lies (an occlusion edge, a newly visible region) and where
+ * the geometry itself moved by more than the tolerance between the two captures.  Nothing else detects a change of the scene: moved lights, changed materials and
+ * geometry that moved by less than the tolerance blend into the history and fade with the cap alone, and a surface that moved ALONG itself is not followed (there are no
+ * motion vectors).  A host that changes the scene in such a way starts a new history.  The geometry and the temporal image of a history slot must belong to the same frame:
+ * capture and reproject every frame, in this order.
+ * Refusals, all checked before anything is launched — the slot's previous temporal image stays valid and untouched.  IDKPT_ERR_INVALID_ARGUMENT: a slot outside the ring
+ * (-1: the current slot; historySlot takes IDKPT_NO_HISTORY or 0 .. frames - 1), slot == historySlot, a PositionTolerance that is not finite and > 0, a MaxHistory that is
+ * not finite and >= 1, a NULL pointer.  (PrevProjView and PrevViewPos are not examined: a value that is not finite can only make a pixel take no history.)
+ * IDKPT_ERR_INVALID_OPERATION: `slot` — also under IDKPT_NO_HISTORY — or the history slot without a geometry image since the last resize, the history slot without a
+ * temporal image, n == 0, no size set, a multi-device context or a context that holds a shard of the rows (the scope of idkptDenoise; idkptCaptureGeometry likewise).
+ * idkptDownloadTemporal (bytes = height * width * 16) and idkptGetTemporalDevicePtr read the temporal image of a slot.
+ * The PositionTolerance and MaxHistory defaults (0.02, 32) are starting values (profiles/reproject.md).
+ *
+ * The consumers.  idkptUseTemporalAsDenoised(ctx, slot) copies the slot's temporal rgb, with alpha 1.0, into its denoised image on the stream — the device-side sibling of
+ * idkptUploadDenoised: idkptSetResultSource(IDKPT_RESULT_DENOISED), idkptPresent, idkptBloom, idkptDownloadDenoised then show it.  enum idkpt_result_source does not grow.
+ * idkptSetDenoiseInput(ctx, input): under IDKPT_DENOISE_INPUT_TEMPORAL idkptDenoise takes c0 from the slot's temporal rgb instead of Result (guides and everything else as
+ * before; IDKPT_ERR_INVALID_OPERATION if the slot holds no temporal image) and idkptDenoiseVariance returns IDKPT_ERR_INVALID_OPERATION (its variance would need per-pixel
+ * sample counts and reprojected moments).  The default is IDKPT_DENOISE_INPUT_ACCUMULATED, under which nothing changes by a bit.  A state of its own, kept by every resize;
+ * a context without the whole frame cannot select TEMPORAL.
+ *
+ * The buffers.  Geometry and temporal image belong to a ring slot, are allocated at the slot's first use — a context that never asks allocates nothing —, each ends with
+ * 64 guard bytes of 0xA5 that nothing writes; released by everything that re-makes the images (idkptSetSize, idkptSetFrameRing with another count, every row-layout
+ * call), KEPT by idkptResetAccumulation, idkptBeginFrame, idkptSetMaxBatch and idkptSetPresentationSize: surviving the reset is their purpose.  A ring of 2 is the
+ * smallest that can reproject (slot and history differ). */
+#define IDKPT_NO_HISTORY (-2)
+typedef struct idkpt_reproject {
+    float   PrevProjView[16];   /* GpuPerFrameData.PrevProjView of the history frame, OpenTK memory order */
+    float   PrevViewPos[3];
+    float   PositionTolerance;  /* > 0, finite; relative to the distance to PrevViewPos.  default 0.02, untuned */
+    float   MaxHistory;         /* >= 1, finite; cap on the history's effective sample count.  default 32, untuned */
+} idkpt_reproject;
+IDKPT_API int32_t idkptCaptureGeometry(idkpt_ctx* ctx, int32_t slot);                                       /* centre rays of the current camera -> the slot's geometry image */
+IDKPT_API int32_t idkptDownloadGeometry(idkpt_ctx* ctx, int32_t slot, float* rgba, size_t bytes);
+IDKPT_API int32_t idkptGetGeometryDevicePtr(idkpt_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes);    /* stream-ordered; the guard bytes follow *outBytes */
+IDKPT_API int32_t idkptReproject(idkpt_ctx* ctx, int32_t slot, int32_t historySlot, const idkpt_reproject* reproject);   /* Result and geometry of the slot, geometry and temporal image of the history slot -> the slot's temporal image */
+IDKPT_API int32_t idkptDownloadTemporal(idkpt_ctx* ctx, int32_t slot, float* rgba, size_t bytes);
+IDKPT_API int32_t idkptGetTemporalDevicePtr(idkpt_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes);    /* stream-ordered; the guard bytes follow *outBytes */
+IDKPT_API int32_t idkptUseTemporalAsDenoised(idkpt_ctx* ctx, int32_t slot);                                   /* the slot's temporal rgb, alpha 1.0 -> its denoised image */
+enum idkpt_denoise_input { IDKPT_DENOISE_INPUT_ACCUMULATED = 0, IDKPT_DENOISE_INPUT_TEMPORAL = 1 };
+IDKPT_API int32_t idkptSetDenoiseInput(idkpt_ctx* ctx, int32_t input);
+IDKPT_API int32_t idkptGetDenoiseInput(idkpt_ctx* ctx, int32_t* outInput);
+
 /* ---- render ----------------------------------------------------------------------------- */
 /* PathTracer.ResetAccumulation (PathTracer.cs:334-337) */
 IDKPT_API int32_t idkptResetAccumulation(idkpt_ctx* ctx);
