@@ -24,6 +24,7 @@ SYMBOLS = [
     "idkptSetNoiseEstimate", "idkptGetNoiseEstimate", "idkptEstimateNoise", "idkptDownloadNoise", "idkptGetNoiseDevicePtr", "idkptDownloadMoments", "idkptGetMomentsDevicePtr",
     "idkptCaptureGeometry", "idkptDownloadGeometry", "idkptGetGeometryDevicePtr", "idkptReproject", "idkptDownloadTemporal", "idkptGetTemporalDevicePtr", "idkptUseTemporalAsDenoised",
     "idkptSetDenoiseInput", "idkptGetDenoiseInput",
+    "idkptReprojectMoments", "idkptDownloadTemporalMoments", "idkptGetTemporalMomentsDevicePtr", "idkptDenoiseTemporal",
 ]
 
 _lib = None
@@ -61,6 +62,8 @@ def load():
         "idkptCaptureGeometry": [vp, i32], "idkptDownloadGeometry": [vp, i32, vp, sz], "idkptGetGeometryDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(sz)], "idkptReproject": [vp, i32, i32, vp],
         "idkptDownloadTemporal": [vp, i32, vp, sz], "idkptGetTemporalDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(sz)], "idkptUseTemporalAsDenoised": [vp, i32],
         "idkptSetDenoiseInput": [vp, i32], "idkptGetDenoiseInput": [vp, C.POINTER(i32)],
+        "idkptReprojectMoments": [vp, i32, i32, vp], "idkptDownloadTemporalMoments": [vp, i32, vp, sz], "idkptGetTemporalMomentsDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(sz)],
+        "idkptDenoiseTemporal": [vp, i32, vp],
         "idkptRefitBlas": [vp, i32], "idkptUploadUnskinnedVertices": [vp, vp, i32], "idkptSkin": [vp, u32, u32, u32, u32],
         "idkptDownloadBuffer": [vp, i32, sz, sz, vp], "idkptResetAccumulation": [vp], "idkptSetSampleSequence": [vp, u32, u32], "idkptGetAccumulatedSamples": [vp, C.POINTER(u32)],
         "idkptRender": [vp], "idkptSynchronize": [vp], "idkptDownload": [vp, i32, vp, sz], "idkptDownloadRays": [vp, vp, sz],

@@ -59,8 +59,8 @@ struct PinnedUpload {
 
 // ---- frame products -----------------------------------------------------------------------------------------------------------------------------------
 // What is made of a finished frame on request: the display image (idkptPresent, host_readback.hpp), the bloom chains (idkptBloom, host_bloom.hpp), the denoised image
-// (idkptDenoise / idkptUploadDenoised, host_denoise.hpp), the noise estimate and the moments images it reads (idkptEstimateNoise, host_noise.hpp), the geometry and temporal
-// images (idkptCaptureGeometry / idkptReproject, host_reproject.hpp).  Their life cycle is
+// (idkptDenoise / idkptUploadDenoised, host_denoise.hpp), the noise estimate and the moments images it reads (idkptEstimateNoise, host_noise.hpp), the geometry, temporal
+// and temporal moments images (idkptCaptureGeometry / idkptReproject / idkptReprojectMoments, host_reproject.hpp).  Their life cycle is
 // stated HERE and nowhere else: the buffers belong to a ring slot and a frame size; they are made at the slot's first use (a context that never asks pays nothing), every
 // buffer ends in GUARD_BYTES of 0xA5 that no kernel writes (include/idkpt.h: what a host or a test looks at to see that nothing ran past the payload); every resize releases
 // them (alloc_frame_impl -> release_all), idkptSetPresentationSize releases those that have the presentation size, idkptSetMaxBatch keeps them (alloc_frame_keep_images moves
@@ -111,11 +111,12 @@ struct NoiseSlot {
     void release() { tiles.release(); summary.release(); valid = false; }
 };
 
-// idkptCaptureGeometry / idkptReproject: the geometry image (world position or miss direction, id bits) and the temporal image (rgb, effective sample count), both RGBA32F
+// idkptCaptureGeometry / idkptReproject / idkptReprojectMoments: the geometry image (world position or miss direction, id bits), the temporal image (rgb, effective sample
+// count) and the temporal moments image (M1, M2, 0, effective sample count), all RGBA32F
 struct TemporalSlot {
-    GuardedBuf geom, temporal;
-    bool geomValid = false, temporalValid = false;                           // captured / reprojected since the last resize
-    void release() { geom.release(); temporal.release(); geomValid = false; temporalValid = false; }
+    GuardedBuf geom, temporal, moments;
+    bool geomValid = false, temporalValid = false, momentsValid = false;     // captured / reprojected / moments reprojected since the last resize
+    void release() { geom.release(); temporal.release(); moments.release(); geomValid = false; temporalValid = false; momentsValid = false; }
 };
 
 static bool slot_holds(const DisplaySlot& s) { return s.format >= 0; }

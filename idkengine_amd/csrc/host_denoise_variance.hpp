@@ -16,7 +16,7 @@ static int32_t dev_DenoiseVariance(dev_ctx* ctx, int32_t slot, const idkpt_denoi
     { int rc = denoise_scope(ctx, "idkptDenoiseVariance"); if (rc) return rc; }
     if (!ctx->st.OutputAOVs) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptDenoiseVariance: the current settings have OutputAOVs = 0: the albedo and normal images that guide the filter are not accumulated");
     { int rc = noise_scope(ctx, "idkptDenoiseVariance"); if (rc) return rc; }
-    if (ctx->denoiseInput == IDKPT_DENOISE_INPUT_TEMPORAL)   // (it would need per-pixel sample counts and reprojected moments: DESIGN.md section 8)
+    if (ctx->denoiseInput == IDKPT_DENOISE_INPUT_TEMPORAL)   // (per-pixel sample counts and reprojected moments are idkptDenoiseTemporal's: host_denoise_temporal.hpp)
         return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptDenoiseVariance: the denoise input is IDKPT_DENOISE_INPUT_TEMPORAL (idkptSetDenoiseInput): the moments are those of the accumulated image, not of the temporal one");
     if (slot < 0) slot = ctx->curSlot;
     const uint32_t samples = ctx->accum[slot];           // (queued samples included: they are launched below)

@@ -1,9 +1,9 @@
 // host_reproject.hpp — idkptCaptureGeometry / idkptDownloadGeometry / idkptGetGeometryDevicePtr / idkptReproject / idkptDownloadTemporal / idkptGetTemporalDevicePtr /
-// idkptUseTemporalAsDenoised / idkptSetDenoiseInput: the geometry image and the temporal image of a ring slot (kernels: kernels_reproject.hpp; the contract: include/idkpt.h,
-// "temporal reprojection").  Part of the single translation unit idkpt.hip (included there, behind host_queries.hpp, whose closest-hit core traces the centre rays, and
+// idkptUseTemporalAsDenoised / idkptSetDenoiseInput / idkptReprojectMoments / idkptDownloadTemporalMoments / idkptGetTemporalMomentsDevicePtr: the geometry image, the temporal
+// image and the temporal moments image of a ring slot (kernels: kernels_reproject.hpp; the contract: include/idkpt.h, "temporal reprojection" and "temporal moments").  Part of the single translation unit idkpt.hip (included there, behind host_queries.hpp, whose closest-hit core traces the centre rays, and
 // host_denoise.hpp, whose scope check and slot record it uses).
 // Queued samples are launched first, nothing but the downloads waits for the GPU.  Frame products (host_context.hpp, "frame products": the life cycle of the buffers): a
-// TemporalSlot per ring slot, both images RGBA32F of the render size; the ray and hit scratch of a capture belongs to the context and is sized for one frame.
+// TemporalSlot per ring slot, all three images RGBA32F of the render size; the ray and hit scratch of a capture belongs to the context and is sized for one frame.
 // One device, the whole frame (the scope of idkptDenoise): a pixel's history may lie in any row.
 #pragma once
 
@@ -35,40 +35,45 @@ static int32_t dev_CaptureGeometry(dev_ctx* ctx, int32_t slot)
     return IDKPT_OK;
 }
 
-// the record of ring slot `slot` (-1: the current one) for the calls that read one of its two images
-static int32_t temporal_slot_of(dev_ctx* ctx, const char* who, int32_t slot, bool geometry, TemporalSlot** out)
+// the record of ring slot `slot` (-1: the current one) for the calls that read one of its three images
+enum TemporalImage { TEMPORAL_IMAGE = 0, GEOMETRY_IMAGE = 1, TEMPORAL_MOMENTS_IMAGE = 2 };
+static bool temporal_holds(const TemporalSlot& s, TemporalImage which) { return which == GEOMETRY_IMAGE ? s.geomValid : which == TEMPORAL_IMAGE ? s.temporalValid : s.momentsValid; }
+static const GuardedBuf& temporal_buf(const TemporalSlot& s, TemporalImage which) { return which == GEOMETRY_IMAGE ? s.geom : which == TEMPORAL_IMAGE ? s.temporal : s.moments; }
+static int32_t temporal_slot_of(dev_ctx* ctx, const char* who, int32_t slot, TemporalImage which, TemporalSlot** out)
 {
     REQUIRE(slot >= -1 && slot < ctx->ringSize, std::string(who) + ": slot outside the frame ring (-1: the current slot)");
     if (slot < 0) slot = ctx->curSlot;
     std::vector<TemporalSlot>& v = ctx->products.temporal;
-    if ((size_t)slot >= v.size() || !(geometry ? v[slot].geomValid : v[slot].temporalValid))
-        return fail(ctx, IDKPT_ERR_INVALID_OPERATION, std::string(who) + (geometry ? ": the slot holds no geometry image since the last resize (idkptCaptureGeometry)" : ": the slot holds no temporal image since the last resize (idkptReproject)"));
+    if ((size_t)slot >= v.size() || !temporal_holds(v[slot], which))
+        return fail(ctx, IDKPT_ERR_INVALID_OPERATION, std::string(who) + (which == GEOMETRY_IMAGE ? ": the slot holds no geometry image since the last resize (idkptCaptureGeometry)" : which == TEMPORAL_IMAGE ? ": the slot holds no temporal image since the last resize (idkptReproject)" : ": the slot holds no temporal moments image since the last resize (idkptReprojectMoments)"));
     *out = &v[slot];
     return IDKPT_OK;
 }
-static int32_t temporal_download(dev_ctx* ctx, const char* who, int32_t slot, bool geometry, float* rgba, size_t bytes)
+static int32_t temporal_download(dev_ctx* ctx, const char* who, int32_t slot, TemporalImage which, float* rgba, size_t bytes)
 {
     if (!ctx || !rgba) return IDKPT_ERR_INVALID_ARGUMENT;
     TemporalSlot* s = nullptr;
-    { int rc = temporal_slot_of(ctx, who, slot, geometry, &s); if (rc) return rc; }
-    const GuardedBuf& b = geometry ? s->geom : s->temporal;
+    { int rc = temporal_slot_of(ctx, who, slot, which, &s); if (rc) return rc; }
+    const GuardedBuf& b = temporal_buf(*s, which);
     REQUIRE(bytes == b.bytes, std::string(who) + ": bytes must equal height*width*16");
     return download_behind_queue(ctx, rgba, b.mem.p, bytes);
 }
-static int32_t temporal_device_ptr(dev_ctx* ctx, const char* who, int32_t slot, bool geometry, void** outPtr, size_t* outBytes)
+static int32_t temporal_device_ptr(dev_ctx* ctx, const char* who, int32_t slot, TemporalImage which, void** outPtr, size_t* outBytes)
 {
     if (!ctx || !outPtr) return IDKPT_ERR_INVALID_ARGUMENT;
     TemporalSlot* s = nullptr;
-    { int rc = temporal_slot_of(ctx, who, slot, geometry, &s); if (rc) return rc; }
-    const GuardedBuf& b = geometry ? s->geom : s->temporal;
+    { int rc = temporal_slot_of(ctx, who, slot, which, &s); if (rc) return rc; }
+    const GuardedBuf& b = temporal_buf(*s, which);
     *outPtr = b.mem.p;
     if (outBytes) *outBytes = b.bytes;
     return IDKPT_OK;
 }
-static int32_t dev_DownloadGeometry(dev_ctx* ctx, int32_t slot, float* rgba, size_t bytes) { return temporal_download(ctx, "idkptDownloadGeometry", slot, true, rgba, bytes); }
-static int32_t dev_GetGeometryDevicePtr(dev_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes) { return temporal_device_ptr(ctx, "idkptGetGeometryDevicePtr", slot, true, outPtr, outBytes); }
-static int32_t dev_DownloadTemporal(dev_ctx* ctx, int32_t slot, float* rgba, size_t bytes) { return temporal_download(ctx, "idkptDownloadTemporal", slot, false, rgba, bytes); }
-static int32_t dev_GetTemporalDevicePtr(dev_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes) { return temporal_device_ptr(ctx, "idkptGetTemporalDevicePtr", slot, false, outPtr, outBytes); }
+static int32_t dev_DownloadGeometry(dev_ctx* ctx, int32_t slot, float* rgba, size_t bytes) { return temporal_download(ctx, "idkptDownloadGeometry", slot, GEOMETRY_IMAGE, rgba, bytes); }
+static int32_t dev_GetGeometryDevicePtr(dev_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes) { return temporal_device_ptr(ctx, "idkptGetGeometryDevicePtr", slot, GEOMETRY_IMAGE, outPtr, outBytes); }
+static int32_t dev_DownloadTemporal(dev_ctx* ctx, int32_t slot, float* rgba, size_t bytes) { return temporal_download(ctx, "idkptDownloadTemporal", slot, TEMPORAL_IMAGE, rgba, bytes); }
+static int32_t dev_GetTemporalDevicePtr(dev_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes) { return temporal_device_ptr(ctx, "idkptGetTemporalDevicePtr", slot, TEMPORAL_IMAGE, outPtr, outBytes); }
+static int32_t dev_DownloadTemporalMoments(dev_ctx* ctx, int32_t slot, float* rgba, size_t bytes) { return temporal_download(ctx, "idkptDownloadTemporalMoments", slot, TEMPORAL_MOMENTS_IMAGE, rgba, bytes); }
+static int32_t dev_GetTemporalMomentsDevicePtr(dev_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes) { return temporal_device_ptr(ctx, "idkptGetTemporalMomentsDevicePtr", slot, TEMPORAL_MOMENTS_IMAGE, outPtr, outBytes); }
 
 static int32_t dev_Reproject(dev_ctx* ctx, int32_t slot, int32_t historySlot, const idkpt_reproject* r)
 {
@@ -108,6 +113,48 @@ static int32_t dev_Reproject(dev_ctx* ctx, int32_t slot, int32_t historySlot, co
     return IDKPT_OK;
 }
 
+// the luminance moments of the slot through the same taps: (m1, m2) of the moments image FinalDraw keeps (host_noise.hpp) blended with the history slot's temporal moments
+// image; independent of idkptReproject (neither reads what the other writes)
+static int32_t dev_ReprojectMoments(dev_ctx* ctx, int32_t slot, int32_t historySlot, const idkpt_reproject* r)
+{
+    if (!ctx || !r) return IDKPT_ERR_INVALID_ARGUMENT;
+    REQUIRE(slot >= -1 && slot < ctx->ringSize, "idkptReprojectMoments: slot outside the frame ring (-1: the current slot)");
+    REQUIRE(historySlot == IDKPT_NO_HISTORY || (historySlot >= 0 && historySlot < ctx->ringSize), "idkptReprojectMoments: historySlot must be IDKPT_NO_HISTORY or a slot of the frame ring");
+    REQUIRE(reprojt::finite(r->PositionTolerance) && r->PositionTolerance > 0.0f, "idkptReprojectMoments: PositionTolerance must be finite and > 0");
+    REQUIRE(reprojt::finite(r->MaxHistory) && r->MaxHistory >= 1.0f, "idkptReprojectMoments: MaxHistory must be finite and >= 1");
+    if (slot < 0) slot = ctx->curSlot;
+    REQUIRE(slot != historySlot, "idkptReprojectMoments: slot and historySlot must differ (a frame is no history of itself)");
+    { int rc = denoise_scope(ctx, "idkptReprojectMoments"); if (rc) return rc; }
+    { int rc = noise_scope(ctx, "idkptReprojectMoments"); if (rc) return rc; }
+    std::vector<TemporalSlot>& v = ctx->products.temporal;
+    auto holds = [&](int q, TemporalImage which) { return (size_t)q < v.size() && temporal_holds(v[q], which); };
+    if (!holds(slot, GEOMETRY_IMAGE)) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptReprojectMoments: the slot holds no geometry image since the last resize (idkptCaptureGeometry)");
+    const bool start = historySlot == IDKPT_NO_HISTORY;
+    if (!start && !holds(historySlot, GEOMETRY_IMAGE)) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptReprojectMoments: the history slot holds no geometry image since the last resize (idkptCaptureGeometry)");
+    if (!start && !holds(historySlot, TEMPORAL_MOMENTS_IMAGE)) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptReprojectMoments: the history slot holds no temporal moments image since the last resize (idkptReprojectMoments)");
+    const uint32_t n = ctx->accum[slot];                 // (queued samples included: they are launched below)
+    if (n == 0u) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptReprojectMoments: the slot has accumulated no sample");
+    HIPC(hipSetDevice(ctx->device));
+    FLUSH_KEEP();                                        // stream-ordered behind what was queued (as idkptReproject)
+    { int rc = check_overflow(ctx); if (rc) return rc; }   // (no wait: see idkptGetFrameDevicePtr)
+    { int rc = noise_moments_ensure(ctx); if (rc) return rc; }
+    const int W = ctx->W, H = ctx->H;
+    TemporalSlot& s = v[slot];
+    s.momentsValid = false;
+    HIPC(s.moments.ensure(ctx->stream, (size_t)W * H * 16));
+    reprojt::Params p;
+    p.W = W; p.H = H;
+    memcpy(p.M, r->PrevProjView, sizeof(p.M)); memcpy(p.prevPos, r->PrevViewPos, sizeof(p.prevPos));
+    p.tol2 = r->PositionTolerance * r->PositionTolerance; p.maxHistory = r->MaxHistory; p.n = (float)n;
+    const dim3 grid((unsigned)((W + reprojk::TILE - 1) / reprojk::TILE), (unsigned)((H + reprojk::TILE - 1) / reprojk::TILE));
+    const float4* hg = start ? nullptr : v[historySlot].geom.as<const float4>();
+    const float4* hm = start ? nullptr : v[historySlot].moments.as<const float4>();
+    hipLaunchKernelGGL(k_reproject_moments, grid, dim3(256), 0, ctx->stream, (const float4*)noise_moments_ptr(ctx, slot), s.geom.as<const float4>(), hg, hm, s.moments.as<float4>(), p);
+    HIPC(hipGetLastError());
+    s.momentsValid = true;
+    return IDKPT_OK;
+}
+
 // the device-side sibling of idkptUploadDenoised: the slot's temporal rgb, alpha 1.0, becomes its denoised image
 static int32_t dev_UseTemporalAsDenoised(dev_ctx* ctx, int32_t slot)
 {
@@ -115,7 +162,7 @@ static int32_t dev_UseTemporalAsDenoised(dev_ctx* ctx, int32_t slot)
     REQUIRE(slot >= -1 && slot < ctx->ringSize, "idkptUseTemporalAsDenoised: slot outside the frame ring (-1: the current slot)");
     { int rc = denoise_scope(ctx, "idkptUseTemporalAsDenoised"); if (rc) return rc; }
     TemporalSlot* t = nullptr;
-    { int rc = temporal_slot_of(ctx, "idkptUseTemporalAsDenoised", slot, false, &t); if (rc) return rc; }
+    { int rc = temporal_slot_of(ctx, "idkptUseTemporalAsDenoised", slot, TEMPORAL_IMAGE, &t); if (rc) return rc; }
     if (slot < 0) slot = ctx->curSlot;
     HIPC(hipSetDevice(ctx->device));
     FLUSH_KEEP();

@@ -955,6 +955,11 @@ int32_t idkptSetDenoiseInput(idkpt_ctx* c, int32_t input)
     return IDKPT_OK;
 }
 int32_t idkptGetDenoiseInput(idkpt_ctx* c, int32_t* outInput) { if (!c || !outInput) return IDKPT_ERR_INVALID_ARGUMENT; return dev_GetDenoiseInput(c->dev[0], outInput); }
+// ---- temporal moments (host_reproject.hpp, host_denoise_temporal.hpp): the reprojected luminance moments and the variance-guided filter on the temporal image
+int32_t idkptReprojectMoments(idkpt_ctx* c, int32_t slot, int32_t historySlot, const idkpt_reproject* reproject) { ONE_ONLY("idkptReprojectMoments", REPROJECT_WHY, dev_ReprojectMoments(m, slot, historySlot, reproject)); }
+int32_t idkptDownloadTemporalMoments(idkpt_ctx* c, int32_t slot, float* rgba, size_t bytes) { ONE_ONLY("idkptDownloadTemporalMoments", REPROJECT_WHY, dev_DownloadTemporalMoments(m, slot, rgba, bytes)); }
+int32_t idkptGetTemporalMomentsDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size_t* outBytes) { ONE_ONLY("idkptGetTemporalMomentsDevicePtr", REPROJECT_WHY, dev_GetTemporalMomentsDevicePtr(m, slot, outPtr, outBytes)); }
+int32_t idkptDenoiseTemporal(idkpt_ctx* c, int32_t slot, const idkpt_denoise_temporal* settings) { ONE_ONLY("idkptDenoiseTemporal", DENOISE_WHY, dev_DenoiseTemporal(m, slot, settings)); }
 
 int32_t idkptResetAccumulation(idkpt_ctx* c) { if (!c) return IDKPT_ERR_INVALID_ARGUMENT; for (dev_ctx* m : c->dev) dev_ResetAccumulation(m); return IDKPT_OK; }
 int32_t idkptSetSampleSequence(idkpt_ctx* c, uint32_t first, uint32_t stride) { REPLICATE(SetSampleSequence, first, stride); }

@@ -10,6 +10,7 @@
 //    the gathers of a tile fall into a tile-sized window of neighbouring lines and the four taps of neighbouring pixels share them (a 1 x 256 strip would touch four times
 //    as many rows of the history images).  Compulsory traffic 32 + 32 B in, 16 B out per pixel: memory-bound.  No LDS (nothing is reused across threads that the cache does
 //    not already serve), no scratch; the camera travels in the kernel arguments.
+//  * k_reproject_moments (idkptReprojectMoments): the same mapping and the same gathers on the slot's luminance moments and the history slot's temporal moments image.
 //  * k_temporal_to_denoised: rgb of the temporal image with alpha 1.0, the denoised image's format.
 #pragma once
 #include "reproject_texel.hpp"
@@ -68,6 +69,23 @@ __global__ __launch_bounds__(256) void k_reproject(const float4* __restrict__ cu
     const float4 r = g[i];
     const MemFetch f = {hg, hc, p.W};
     const reprojt::V4 o = reprojt::reproject_texel(f, p, reprojt::v4(c.x, c.y, c.z, c.w), reprojt::v4(r.x, r.y, r.z, r.w));
+    out[i] = make_float4(o.x, o.y, o.z, o.w);
+}
+
+// idkptReprojectMoments: k_reproject's grid, thread mapping and traffic on the luminance moments.  mom: the slot's moments image (m1, m2, 0, 1); hg / hm: the history
+// slot's geometry and temporal moments images, or both null to start a history (out = (m1, m2, 0, n)).  No LDS, no scratch.
+__global__ __launch_bounds__(256) void k_reproject_moments(const float4* __restrict__ mom, const float4* __restrict__ g, const float4* __restrict__ hg, const float4* __restrict__ hm,
+                                                           float4* __restrict__ out, reprojt::Params p)
+{
+    using namespace reprojk;
+    const int x = (int)blockIdx.x * TILE + ((int)threadIdx.x & (TILE - 1)), y = (int)blockIdx.y * TILE + ((int)threadIdx.x >> 4);
+    if (x >= p.W || y >= p.H) return;
+    const size_t i = (size_t)y * (size_t)p.W + (size_t)x;
+    const float4 m = mom[i];
+    if (!hg) { out[i] = make_float4(m.x, m.y, 0.0f, p.n); return; }
+    const float4 r = g[i];
+    const MemFetch f = {hg, hm, p.W};
+    const reprojt::V4 o = reprojt::reproject_moments_texel(f, p, m.x, m.y, reprojt::v4(r.x, r.y, r.z, r.w));
     out[i] = make_float4(o.x, o.y, o.z, o.w);
 }
 

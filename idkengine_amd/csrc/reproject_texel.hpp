@@ -94,4 +94,15 @@ REPROJECT_HD V4 reproject_texel(const Fetch& fetch, const Params& P, V4 cur, V4 
     return v4((hr * Hc + cur.x * P.n) / den, (hgr * Hc + cur.y * P.n) / den, (hb * Hc + cur.z * P.n) / den, den);
 }
 
+// One pixel of idkptReprojectMoments: the same clip coordinates, taps, validity rules and blend on the luminance moments.  (m1, m2) of the slot's moments image, g its
+// geometry record; fetch returns the history slot's geometry record and TEMPORAL MOMENTS texel (M1, M2, 0, cnt).  Returns (M1, M2, 0, effective sample count): the third
+// channel is stored as 0 whatever the history held there.
+template <class Fetch>
+REPROJECT_HD V4 reproject_moments_texel(const Fetch& fetch, const Params& P, float m1, float m2, V4 g)
+{
+    V4 o = reproject_texel(fetch, P, v4(m1, m2, 0.0f, 0.0f), g);
+    o.z = 0.0f;
+    return o;
+}
+
 }  // namespace reprojt

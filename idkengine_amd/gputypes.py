@@ -209,6 +209,17 @@ class DenoiseVariance(C.Structure):
         super().__init__(int(Iterations), float(LumaSigma), float(VarianceEpsilon), float(AlbedoSigma), float(NormalSigma), int(DemodulateAlbedo))
 
 
+class DenoiseTemporal(C.Structure):
+    """idkpt_denoise_temporal: the settings of idkptDenoiseTemporal (include/idkpt.h, "temporal moments"; no counterpart in the reference).  DenoiseVariance's fields and
+    SpatialBelow: pixels whose effective sample count is below it take the 7 x 7 spatial estimate of the variance.  The defaults are starting values
+    (profiles/denoise_temporal.md)."""
+    _fields_ = [("Iterations", C.c_int32), ("LumaSigma", C.c_float), ("VarianceEpsilon", C.c_float), ("AlbedoSigma", C.c_float), ("NormalSigma", C.c_float), ("DemodulateAlbedo", C.c_int32),
+                ("SpatialBelow", C.c_float)]
+
+    def __init__(self, Iterations=5, LumaSigma=1.0, VarianceEpsilon=0.1, AlbedoSigma=0.2, NormalSigma=0.5, DemodulateAlbedo=True, SpatialBelow=4.0):
+        super().__init__(int(Iterations), float(LumaSigma), float(VarianceEpsilon), float(AlbedoSigma), float(NormalSigma), int(DemodulateAlbedo), float(SpatialBelow))
+
+
 class Noise(C.Structure):
     """idkpt_noise: the settings of idkptEstimateNoise (include/idkpt.h, "noise estimate"; no counterpart in the reference).  The defaults are starting values nobody has
     tuned (profiles/noise.md)."""

@@ -749,6 +749,41 @@ class PathTracer:
         self._check(self._L.idkptGetDenoiseInput(self._ctx, C.byref(s)))
         return s.value
 
+    # ---- temporal moments (idkptReprojectMoments / idkptDenoiseTemporal): the variance-guided filter on the reprojected frame; no counterpart in the reference
+    def ReprojectMoments(self, slot=None, history=T.IDKPT_NO_HISTORY, settings=None):
+        """idkptReprojectMoments: blends the luminance moments of `slot` (SetNoiseEstimate(True)) with the temporal moments image of ring slot `history` through the taps of
+        Reproject (settings: the same gputypes.Reproject); history = IDKPT_NO_HISTORY starts a history.  Both slots need CaptureGeometry first.  The result stays in the
+        slot's temporal moments image (DownloadTemporalMoments)."""
+        if settings is None:
+            settings = T.Reproject()
+        if not isinstance(settings, T.Reproject):
+            raise TypeError("ReprojectMoments: settings must be a gputypes.Reproject")
+        self._check(self._L.idkptReprojectMoments(self._ctx, -1 if slot is None else int(slot), int(history), C.addressof(settings)))
+
+    def DownloadTemporalMoments(self, slot=None):
+        """idkptDownloadTemporalMoments: (H, W, 4) float32 — (M1, M2, 0, the effective sample count)"""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.idkptDownloadTemporalMoments(self._ctx, -1 if slot is None else int(slot), out.ctypes.data, out.nbytes))
+        return out
+
+    def temporal_moments_device_ptr(self, slot=None):
+        """idkptGetTemporalMomentsDevicePtr: (device pointer, bytes), valid in stream order; 64 guard bytes follow"""
+        p = C.c_void_p(); n = C.c_size_t()
+        self._check(self._L.idkptGetTemporalMomentsDevicePtr(self._ctx, -1 if slot is None else int(slot), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def DenoiseTemporal(self, settings=None, slot=None):
+        """idkptDenoiseTemporal + idkptDownloadDenoised: the variance-guided a-trous filter over the TEMPORAL image of ring slot `slot` (None: the current one), its variance
+        from the slot's temporal moments image (needs OutputAOVs, Reproject and ReprojectMoments), as an (H, W, 4) float32 array (rgb, 1.0).  settings: a
+        gputypes.DenoiseTemporal; None = the defaults.  It fills the image Denoise fills: Present and Bloom read it under IDKPT_RESULT_DENOISED."""
+        if settings is None:
+            settings = T.DenoiseTemporal()
+        if not isinstance(settings, T.DenoiseTemporal):
+            raise TypeError("DenoiseTemporal: settings must be a gputypes.DenoiseTemporal")
+        slot = -1 if slot is None else int(slot)
+        self._check(self._L.idkptDenoiseTemporal(self._ctx, slot, C.addressof(settings)))
+        return self.DownloadDenoised(slot)
+
     def enable_counters(self, on=True):
         self._check(self._L.idkptEnableCounters(self._ctx, 1 if on else 0))
 

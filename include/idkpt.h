@@ -876,8 +876,8 @@ IDKPT_API int32_t idkptDenoiseVariance(idkpt_ctx* ctx, int32_t slot, const idkpt
  * The consumers.  idkptUseTemporalAsDenoised(ctx, slot) copies the slot's temporal rgb, with alpha 1.0, into its denoised image on the stream — the device-side sibling of
  * idkptUploadDenoised: idkptSetResultSource(IDKPT_RESULT_DENOISED), idkptPresent, idkptBloom, idkptDownloadDenoised then show it.  enum idkpt_result_source does not grow.
  * idkptSetDenoiseInput(ctx, input): under IDKPT_DENOISE_INPUT_TEMPORAL idkptDenoise takes c0 from the slot's temporal rgb instead of Result (guides and everything else as
- * before; IDKPT_ERR_INVALID_OPERATION if the slot holds no temporal image) and idkptDenoiseVariance returns IDKPT_ERR_INVALID_OPERATION (its variance would need per-pixel
- * sample counts and reprojected moments).  The default is IDKPT_DENOISE_INPUT_ACCUMULATED, under which nothing changes by a bit.  A state of its own, kept by every resize;
+ * before; IDKPT_ERR_INVALID_OPERATION if the slot holds no temporal image) and idkptDenoiseVariance returns IDKPT_ERR_INVALID_OPERATION (its variance is that of the accumulated
+ * mean; the filter for the temporal image is idkptDenoiseTemporal, "temporal moments" below).  The default is IDKPT_DENOISE_INPUT_ACCUMULATED, under which nothing changes by a bit.  A state of its own, kept by every resize;
  * a context without the whole frame cannot select TEMPORAL.
  *
  * The buffers.  Geometry and temporal image belong to a ring slot, are allocated at the slot's first use — a context that never asks allocates nothing —, each ends with
@@ -901,6 +901,72 @@ IDKPT_API int32_t idkptUseTemporalAsDenoised(idkpt_ctx* ctx, int32_t slot);     
 enum idkpt_denoise_input { IDKPT_DENOISE_INPUT_ACCUMULATED = 0, IDKPT_DENOISE_INPUT_TEMPORAL = 1 };
 IDKPT_API int32_t idkptSetDenoiseInput(idkpt_ctx* ctx, int32_t input);
 IDKPT_API int32_t idkptGetDenoiseInput(idkpt_ctx* ctx, int32_t* outInput);
+
+/* ---- temporal moments (added under the same ABI number; detect by symbol): a variance-guided filter for the reprojected frame ------------------------------------------
+ * THIS HAS NO COUNTERPART IN THE REFERENCE.  The third piece of SVGF (Schied et al. 2017): right after a camera move a host holds a temporal image and a one-sample frame;
+ * idkptDenoiseVariance refuses both (N < 2, and the temporal input), and idkptDenoise has one ColorSigma for a pixel with 30 samples of history and for a freshly
+ * disoccluded one.  The calls of this section reproject the LUMINANCE MOMENTS with the taps of the colour, turn them into a per-pixel variance of the mean with each
+ * pixel's own effective sample count — estimated spatially where the history is too short to trust — and run idkptDenoiseVariance's iterations on the temporal image.
+ * Everything is default-off and additive: no existing call, struct, enum or image changes by a bit; enum idkpt_denoise_input does not grow and idkptDenoiseTemporal
+ * ignores idkptSetDenoiseInput.  Every operation of the texts below is a correctly rounded binary32 + - * / or floorf in the written order (-ffp-contract=off), sums run
+ * in the order written, so the texts define the results BIT FOR BIT; they are checked against an independent numpy restatement (tests/denoise_temporal_ref.py).
+ *
+ * The temporal moments image.  A third image of the ring slot beside its geometry and temporal images: RGBA32F of the render size, (M1, M2, 0, cnt) per pixel — the first
+ * two moments of the luminance over the pixel's history and the effective sample count behind them.  Allocated at its first use, followed by 64 guard bytes of 0xA5 that
+ * nothing writes; released by everything that releases the geometry and temporal images (idkptSetSize, idkptSetFrameRing with another count, every row-layout call), KEPT
+ * by idkptResetAccumulation, idkptBeginFrame, idkptSetMaxBatch, idkptSetPresentationSize and by idkptSetNoiseEstimate in either direction.
+ *
+ * idkptReprojectMoments(ctx, slot, historySlot, r) writes the temporal moments image of `slot`.  The settings struct and the IDKPT_NO_HISTORY rule are idkptReproject's.
+ * Inputs: (m1, m2) of the slot's moments image (the one idkptSetNoiseEstimate keeps); n = (float) of the slot's sample count (>= 1; queued samples are launched first);
+ * g = the geometry image of `slot`; hg = the geometry image and hm = the temporal moments image of `historySlot`.
+ * historySlot == IDKPT_NO_HISTORY starts a history: out = (m1, m2, 0, n) at every pixel.  Otherwise clip coordinates, previous pixel position, the four taps, their weights
+ * and their order are the text of idkptReproject verbatim.  A tap q is VALID iff it lies inside the image; the id bits of hg_q equal id; for a hit, the position test of
+ * idkptReproject passes; and all four channels c of hm_q satisfy fabsf(c) <= FLT_MAX.
+ *   Blend.  Over the valid taps in order: sum += hm_q * w per channel (all four), sumW += w.  If sumW >= 0.01f:
+ *       h = sum / sumW per channel;  Hc = fminf(h.a, MaxHistory);
+ *       out.M1 = (h.M1 * Hc + m1 * n) / (Hc + n);  out.M2 likewise;  out.z = 0;  out.a = Hc + n.
+ *     Otherwise, and wherever the text of idkptReproject says "no history": out = (m1, m2, 0, n).
+ * With finite inputs and history images of the same frame, out.a equals the alpha of idkptReproject's temporal image bit for bit.  The call is stream-ordered, waits for
+ * nothing and touches no other image; it is independent of idkptReproject (neither needs the other's output; either order after the capture).
+ * Refusals, all checked before anything is launched — the slot's previous temporal moments image stays valid and untouched.  IDKPT_ERR_INVALID_ARGUMENT: idkptReproject's
+ * argument checks.  IDKPT_ERR_INVALID_OPERATION: the noise-estimate switch is off (no moments are kept); `slot` — also under IDKPT_NO_HISTORY — or the history slot without
+ * a geometry image; the history slot without a temporal moments image; n == 0; no size set, a multi-device context or a context that holds a shard of the rows.
+ * idkptDownloadTemporalMoments (bytes = height * width * 16) and idkptGetTemporalMomentsDevicePtr read the image as idkptDownloadTemporal / idkptGetTemporalDevicePtr do.
+ *
+ * idkptDenoiseTemporal(ctx, slot, d) fills the slot's denoised image — the fourth way to fill it: the buffers are idkptDenoise's, and idkptDownloadDenoised,
+ * idkptGetDenoisedDevicePtr, idkptGetDenoiseRoute, idkptSetResultSource, idkptPresent and idkptBloom work on its result unchanged.
+ * Inputs per pixel.  t = the slot's temporal rgb (its alpha is not read); (M1, M2, cnt) = channels x, y, w of the slot's temporal moments image; a = Albedo.rgb,
+ * n = Normal.rgb of the slot as accumulated; lum, floor, invA, invN, d(u) and |d|^2 as in idkptDenoiseVariance's text.
+ * The first state (c0, v0):
+ *   If M1, M2 or cnt is not finite: v0 = +Inf.
+ *   Else if cnt >= SpatialBelow: v0 = fmaxf(M2 - M1 * M1, 0.0f) / (cnt - 1).
+ *   Else the spatial estimate.  Taps q = p + (dx, dy), dy the outer loop over -3 .. 3, dx the inner one; a tap outside the image is SKIPPED;
+ *       w = 1 / ((1 + |d(a)|^2 * invA) * (1 + |d(n)|^2 * invN));
+ *       the tap contributes iff w > 0 and M1_q and M2_q are finite: sM1 += M1_q * w, sM2 += M2_q * w, sW += w.
+ *     If sW == 0: v0 = +Inf.  Otherwise a1 = sM1 / sW, a2 = sM2 / sW, v0 = fmaxf(a2 - a1 * a1, 0.0f) / cnt.
+ *   Then, as idkptDenoiseVariance makes its first state: c0 = t; if DemodulateAlbedo: c0 = t / floor(a) per channel, la = lum(floor(a)), v0 = v0 / (la * la).
+ * A count of 0 or a negative count only yields a v0 that is not finite, or one the iterations treat as written.  No value feeds an address.
+ * The iterations.  Steps 1 - 5 of idkptDenoiseVariance's text on the state (c0, v0), and its final remodulation and alpha of 1.0, verbatim.
+ * The call is stream-ordered behind queued samples and waits for nothing; it reads the temporal image, the temporal moments image, Albedo and Normal and changes none of
+ * them, nor the accumulation.  It needs neither the noise-estimate switch nor two samples.
+ * Refusals, all checked before anything is launched — the slot's previous denoised image stays valid and untouched.  IDKPT_ERR_INVALID_ARGUMENT: a slot outside the ring,
+ * Iterations outside 1..8, a LumaSigma, VarianceEpsilon, AlbedoSigma or NormalSigma that is not finite and > 0, a SpatialBelow that is not finite or < 2, DemodulateAlbedo
+ * other than 0 / 1, a NULL pointer.  IDKPT_ERR_INVALID_OPERATION: the slot holds no temporal image or no temporal moments image; OutputAOVs == 0; no size set; a context
+ * without the whole frame.
+ * SpatialBelow = 4 is SVGF's value; it and the other defaults (idkptDenoiseVariance's) are untuned here (profiles/denoise_temporal.md). */
+typedef struct idkpt_denoise_temporal {
+    int32_t Iterations;        /* 1..8; iteration i uses tap spacing 1 << i.  default 5 */
+    float   LumaSigma;         /* > 0, finite.  default 1.0 */
+    float   VarianceEpsilon;   /* > 0, finite.  default 0.1 */
+    float   AlbedoSigma;       /* > 0, finite.  default 0.2 */
+    float   NormalSigma;       /* > 0, finite.  default 0.5 */
+    int32_t DemodulateAlbedo;  /* 0 / 1.  default 1 */
+    float   SpatialBelow;      /* >= 2, finite; pixels whose effective sample count is below it take the spatial estimate.  default 4 (SVGF's value, untuned here) */
+} idkpt_denoise_temporal;
+IDKPT_API int32_t idkptReprojectMoments(idkpt_ctx* ctx, int32_t slot, int32_t historySlot, const idkpt_reproject* reproject);   /* moments and geometry of the slot, geometry and temporal moments of the history slot -> the slot's temporal moments image */
+IDKPT_API int32_t idkptDownloadTemporalMoments(idkpt_ctx* ctx, int32_t slot, float* rgba, size_t bytes);
+IDKPT_API int32_t idkptGetTemporalMomentsDevicePtr(idkpt_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes);   /* stream-ordered; the guard bytes follow *outBytes */
+IDKPT_API int32_t idkptDenoiseTemporal(idkpt_ctx* ctx, int32_t slot, const idkpt_denoise_temporal* settings);        /* temporal image, temporal moments, Albedo and Normal of the slot -> its denoised image */
 
 /* ---- render ----------------------------------------------------------------------------- */
 /* PathTracer.ResetAccumulation (PathTracer.cs:334-337) */
