@@ -59,12 +59,7 @@ DENOISE_HD State temporal_state(const Fetch& fetch, int W, int H, int x, int y, 
     if (!noiset::finite(M1) || !noiset::finite(M2) || !noiset::finite(cnt)) st.v = INFINITY;
     else if (cnt >= spatialBelow) st.v = fmaxf(M2 - M1 * M1, 0.0f) / (cnt - 1.0f);
     else st.v = spatial_variance(fetch, W, H, x, y, cnt, a, n, invA, invN);
-    if (demod) {                          // as denoisevt::first_state
-        st.c = denoiset::demodulate(t, a);
-        const float la = denoisevt::lum(v3(denoiset::albedo_floor(a.x), denoiset::albedo_floor(a.y), denoiset::albedo_floor(a.z)));
-        st.v = st.v / (la * la);
-    }
-    return st;
+    return demod ? denoisevt::demodulate_state(st, a) : st;
 }
 
 }  // namespace denoisett

@@ -33,16 +33,19 @@ DENOISE_HD float variance_of_mean(float m1, float m2, uint32_t n)
     return fmaxf(m2 - m1 * m1, 0.0f) / (float)(n - 1u);
 }
 
-// the state the first iteration reads: (Result.rgb, v0), demodulated by the pixel's own floored albedo when `demod` (the variance by the square of its luminance)
+// a state demodulated by its pixel's own floored albedo, the variance by the square of that albedo's luminance (the end of first_state and of denoisett::temporal_state)
+DENOISE_HD State demodulate_state(State st, V3 albedo)
+{
+    st.c = denoiset::demodulate(st.c, albedo);
+    const float la = lum(v3(denoiset::albedo_floor(albedo.x), denoiset::albedo_floor(albedo.y), denoiset::albedo_floor(albedo.z)));
+    st.v = st.v / (la * la);
+    return st;
+}
+// the state the first iteration reads: (Result.rgb, v0), demodulated when `demod`
 DENOISE_HD State first_state(V3 result, float m1, float m2, uint32_t n, V3 albedo, bool demod)
 {
     State st; st.c = result; st.v = variance_of_mean(m1, m2, n);
-    if (demod) {
-        st.c = denoiset::demodulate(result, albedo);
-        const float la = lum(v3(denoiset::albedo_floor(albedo.x), denoiset::albedo_floor(albedo.y), denoiset::albedo_floor(albedo.z)));
-        st.v = st.v / (la * la);
-    }
-    return st;
+    return demod ? demodulate_state(st, albedo) : st;
 }
 
 // One iteration at pixel (x, y) of a W x H image with tap spacing s.  fetch(qx, qy, &st, &a, &n) returns the state of the previous iteration (first_state for the first),

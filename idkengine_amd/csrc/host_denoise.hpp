@@ -1,5 +1,6 @@
 // host_denoise.hpp — idkptDenoise / idkptUploadDenoised / idkptDownloadDenoised / idkptGetDenoisedDevicePtr / idkptGetDenoiseRoute / idkptSetResultSource: the denoised
-// image of a ring slot (kernels: kernels_denoise.hpp; the contract: include/idkpt.h).  Part of the single translation unit idkpt.hip (included there, in this order).
+// image of a ring slot (kernels: kernels_denoise.hpp; the contract: include/idkpt.h), and the driver the three a-trous filters share (denoise_check, denoise_begin,
+// denoise_iterate, denoise_ladder).  Part of the single translation unit idkpt.hip (included there, in this order).
 // Queued samples are launched first, nothing but the download waits for the GPU.  A frame product (host_context.hpp, "frame products": the life cycle of the buffers): the
 // denoised image and the two images the iterations alternate between, all RGBA32F of the render size.
 // One device, the whole frame: the taps of iteration i reach 2 * 2^i rows, a shard of the rows would need halos as tall as that.
@@ -13,48 +14,91 @@ static int32_t denoise_scope(dev_ctx* ctx, const char* who)
     if (!owns_whole_frame(ctx)) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, std::string(who) + ": the context holds a shard of the rows (idkptSetRowSharding / idkptSetRowBands / idkptSetRowRange) or is a member of a multi-device context; the denoised image needs the whole frame on one device");
     return IDKPT_OK;
 }
+
+// ---- the driver of the calls that fill a DenoiseSlot by a-trous iterations: idkptDenoise below, idkptDenoiseVariance (host_denoise_variance.hpp), idkptDenoiseTemporal
+// (host_denoise_temporal.hpp).  A filter is: denoise_check, what else it refuses, denoise_begin, its Params, denoise_iterate with a callable that launches one iteration.
+// The checks in the order every filter refuses.  The filter judges its own arguments and hands over the message of those that failed (nullptr: none): ownBefore for the
+// ones checked before DemodulateAlbedo (its sigmas), ownAfter for the ones behind it.
+static int32_t denoise_check(dev_ctx* ctx, const std::string& who, int32_t slot, int32_t iterations, int32_t demodulate, const char* ownBefore, const char* ownAfter = nullptr)
+{
+    REQUIRE(slot >= -1 && slot < ctx->ringSize, who + ": slot outside the frame ring (-1: the current slot)");
+    REQUIRE(iterations >= 1 && iterations <= denoiset::MAX_ITERATIONS, who + ": Iterations must be 1..8");
+    REQUIRE(!ownBefore, who + ownBefore);
+    REQUIRE(demodulate == 0 || demodulate == 1, who + ": DemodulateAlbedo must be 0 or 1");
+    REQUIRE(!ownAfter, who + ownAfter);
+    { int rc = denoise_scope(ctx, who.c_str()); if (rc) return rc; }
+    if (!ctx->st.OutputAOVs) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, who + ": the current settings have OutputAOVs = 0: the albedo and normal images that guide the filter are not accumulated");
+    return IDKPT_OK;
+}
+// the record of a slot whose denoised image is about to be made (by a filter, an upload or idkptUseTemporalAsDenoised): it holds none until its maker says so
+static DenoiseSlot& denoise_slot_invalidated(dev_ctx* ctx, int32_t slot) { DenoiseSlot& s = FrameProducts::slot(ctx->products.denoise, ctx->ringSize, slot); s.valid = false; s.iterations = 0; return s; }
+
+struct DenoiseFill { DenoiseSlot* s; int W, H, n; const float4* albedo; const float4* normal; dim3 grid; };   // what denoise_begin hands over: the slot, the guides, a workgroup per 16 x 16 tile
+// Queued samples are launched, `between` (or nullptr) runs, the slot is invalidated and its images are made.  Iteration i writes ping[i & 1] and the last one `out`: ping[0]
+// is needed from 2 iterations on, ping[1] from 3 — or always, where the image the first iteration reads lives in ping[1] (firstInPing1: a pre-pass of the filter makes it).
+static int32_t denoise_begin(dev_ctx* ctx, int32_t slot, int n, bool firstInPing1, int (*between)(dev_ctx*), DenoiseFill* f)
+{
+    HIPC(hipSetDevice(ctx->device));
+    FLUSH_KEEP();                                        // stream-ordered behind what was queued (as idkptBloom)
+    { int rc = check_overflow(ctx); if (rc) return rc; }   // (no wait: see idkptGetFrameDevicePtr)
+    if (between) { int rc = between(ctx); if (rc) return rc; }
+    f->W = ctx->W; f->H = ctx->H; f->n = n; f->s = &denoise_slot_invalidated(ctx, slot);
+    const size_t bytes = (size_t)f->W * f->H * 16;
+    HIPC(f->s->out.ensure(ctx->stream, bytes));
+    if (n >= 2) HIPC(f->s->ping[0].ensure(ctx->stream, bytes));
+    if (n >= 3 || firstInPing1) HIPC(f->s->ping[1].ensure(ctx->stream, bytes));
+    f->albedo = image_ptr(ctx, IDKPT_IMAGE_ALBEDO, slot); f->normal = image_ptr(ctx, IDKPT_IMAGE_NORMAL, slot);
+    f->grid = dim3((unsigned)((f->W + denoisek::TILE - 1) / denoisek::TILE), (unsigned)((f->H + denoisek::TILE - 1) / denoisek::TILE));
+    return IDKPT_OK;
+}
+// launch(i, spacing, route, src, dst, first, last) launches iteration i, which reads `src`: the caller's for the first, then the image the previous one wrote
+template <class Launch>
+static int32_t denoise_iterate(dev_ctx* ctx, const DenoiseFill& f, const float4* src, const Launch& launch)
+{
+    DenoiseSlot& s = *f.s;
+    for (int i = 0, n = f.n; i < n; i++) {
+        float4* dst = (i == n - 1 ? s.out : s.ping[i & 1]).as<float4>();
+        s.route[i] = (uint8_t)denoise_route(1 << i);
+        launch(i, 1 << i, (int)s.route[i], src, dst, i == 0, i == n - 1);
+        src = dst;
+    }
+    HIPC(hipGetLastError());
+    s.iterations = f.n; s.valid = true;
+    return IDKPT_OK;
+}
+// the spacing ladder of a kernel family: direct() launches its direct kernel, tile(DenoiseSpacing<S>()) its tiled kernel's instance for spacing S = 1, 2 or 4
+template <int S> struct DenoiseSpacing { static constexpr int value = S; };
+template <class Tile, class Direct>
+static void denoise_ladder(int route, int spacing, const Tile& tile, const Direct& direct)
+{
+    if (route == IDKPT_DENOISE_ROUTE_DIRECT) direct();
+    else if (spacing == 1) tile(DenoiseSpacing<1>());
+    else if (spacing == 2) tile(DenoiseSpacing<2>());
+    else tile(DenoiseSpacing<4>());
+}
+
 static int32_t dev_Denoise(dev_ctx* ctx, int32_t slot, const idkpt_denoise* d)
 {
     if (!ctx || !d) return IDKPT_ERR_INVALID_ARGUMENT;
-    REQUIRE(slot >= -1 && slot < ctx->ringSize, "idkptDenoise: slot outside the frame ring (-1: the current slot)");
-    REQUIRE(d->Iterations >= 1 && d->Iterations <= denoiset::MAX_ITERATIONS, "idkptDenoise: Iterations must be 1..8");
     auto sigma = [](float v) { return v - v == 0.0f && v > 0.0f; };
-    REQUIRE(sigma(d->ColorSigma) && sigma(d->AlbedoSigma) && sigma(d->NormalSigma), "idkptDenoise: ColorSigma, AlbedoSigma and NormalSigma must be finite and > 0");
-    REQUIRE(d->DemodulateAlbedo == 0 || d->DemodulateAlbedo == 1, "idkptDenoise: DemodulateAlbedo must be 0 or 1");
-    { int rc = denoise_scope(ctx, "idkptDenoise"); if (rc) return rc; }
-    if (!ctx->st.OutputAOVs) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptDenoise: the current settings have OutputAOVs = 0: the albedo and normal images that guide the filter are not accumulated");
+    const bool sigmas = sigma(d->ColorSigma) && sigma(d->AlbedoSigma) && sigma(d->NormalSigma);
+    { int rc = denoise_check(ctx, "idkptDenoise", slot, d->Iterations, d->DemodulateAlbedo, sigmas ? nullptr : ": ColorSigma, AlbedoSigma and NormalSigma must be finite and > 0"); if (rc) return rc; }
     if (slot < 0) slot = ctx->curSlot;
     const bool temporalIn = ctx->denoiseInput == IDKPT_DENOISE_INPUT_TEMPORAL;   // idkptSetDenoiseInput: c0 is the slot's temporal rgb (host_reproject.hpp)
     if (temporalIn && !((size_t)slot < ctx->products.temporal.size() && ctx->products.temporal[slot].temporalValid))
         return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptDenoise: the denoise input is IDKPT_DENOISE_INPUT_TEMPORAL and the slot holds no temporal image since the last resize (idkptReproject)");
-    HIPC(hipSetDevice(ctx->device));
-    FLUSH_KEEP();                                        // stream-ordered behind what was queued (as idkptBloom)
-    { int rc = check_overflow(ctx); if (rc) return rc; }   // (no wait: see idkptGetFrameDevicePtr)
-    const int W = ctx->W, H = ctx->H, n = d->Iterations;
-    const size_t bytes = (size_t)W * H * 16;
-    DenoiseSlot& s = FrameProducts::slot(ctx->products.denoise, ctx->ringSize, slot);
-    s.valid = false; s.iterations = 0;
-    HIPC(s.out.ensure(ctx->stream, bytes));
-    for (int k = 0; k < 2 && k < n - 1; k++) HIPC(s.ping[k].ensure(ctx->stream, bytes));
-    const float4* albedo = image_ptr(ctx, IDKPT_IMAGE_ALBEDO, slot); const float4* normal = image_ptr(ctx, IDKPT_IMAGE_NORMAL, slot);
-    const dim3 grid((unsigned)((W + denoisek::TILE - 1) / denoisek::TILE), (unsigned)((H + denoisek::TILE - 1) / denoisek::TILE));
-    const float4* src = temporalIn ? ctx->products.temporal[slot].temporal.as<const float4>() : image_ptr(ctx, IDKPT_IMAGE_RESULT, slot);
-    for (int i = 0; i < n; i++) {
-        float4* dst = (i == n - 1 ? s.out : s.ping[i & 1]).as<float4>();
-        denoisek::Params p;
-        p.W = W; p.H = H; p.s = 1 << i;
-        p.invC = denoiset::inv_sigma2(d->ColorSigma, i); p.invA = denoiset::inv_sigma2(d->AlbedoSigma, 0); p.invN = denoiset::inv_sigma2(d->NormalSigma, 0);
-        p.demodIn = d->DemodulateAlbedo && i == 0; p.remodOut = d->DemodulateAlbedo && i == n - 1;
-        s.route[i] = (uint8_t)denoise_route(p.s);
-        if (s.route[i] == IDKPT_DENOISE_ROUTE_DIRECT) hipLaunchKernelGGL(k_denoise_direct, grid, dim3(256), 0, ctx->stream, src, albedo, normal, dst, p);
-        else if (p.s == 1) hipLaunchKernelGGL((k_denoise_tile<1>), grid, dim3(256), 0, ctx->stream, src, albedo, normal, dst, p);
-        else if (p.s == 2) hipLaunchKernelGGL((k_denoise_tile<2>), grid, dim3(256), 0, ctx->stream, src, albedo, normal, dst, p);
-        else hipLaunchKernelGGL((k_denoise_tile<4>), grid, dim3(256), 0, ctx->stream, src, albedo, normal, dst, p);
-        src = dst;
-    }
-    HIPC(hipGetLastError());
-    s.iterations = n; s.valid = true;
-    return IDKPT_OK;
+    DenoiseFill f;
+    { int rc = denoise_begin(ctx, slot, d->Iterations, false, nullptr, &f); if (rc) return rc; }
+    denoisek::Params p;
+    p.W = f.W; p.H = f.H; p.invA = denoiset::inv_sigma2(d->AlbedoSigma, 0); p.invN = denoiset::inv_sigma2(d->NormalSigma, 0);
+    const float4* c0 = temporalIn ? ctx->products.temporal[slot].temporal.as<const float4>() : image_ptr(ctx, IDKPT_IMAGE_RESULT, slot);
+    return denoise_iterate(ctx, f, c0, [&](int i, int spacing, int route, const float4* src, float4* dst, bool first, bool last) {
+        p.s = spacing; p.invC = denoiset::inv_sigma2(d->ColorSigma, i);
+        p.demodIn = d->DemodulateAlbedo && first; p.remodOut = d->DemodulateAlbedo && last;
+        denoise_ladder(route, spacing,
+            [&](auto S) { hipLaunchKernelGGL((k_denoise_tile<decltype(S)::value>), f.grid, dim3(256), 0, ctx->stream, src, f.albedo, f.normal, dst, p); },
+            [&] { hipLaunchKernelGGL(k_denoise_direct, f.grid, dim3(256), 0, ctx->stream, src, f.albedo, f.normal, dst, p); });
+    });
 }
 
 // the host's own denoiser's output (the reference's denoisedTexture.Upload2D): the array is borrowed for the call only and the copy must not make the call wait for the
@@ -69,8 +113,7 @@ static int32_t dev_UploadDenoised(dev_ctx* ctx, int32_t slot, const float* rgba,
     if (slot < 0) slot = ctx->curSlot;
     HIPC(hipSetDevice(ctx->device));
     FLUSH_KEEP();
-    DenoiseSlot& s = FrameProducts::slot(ctx->products.denoise, ctx->ringSize, slot);
-    s.valid = false; s.iterations = 0;
+    DenoiseSlot& s = denoise_slot_invalidated(ctx, slot);
     HIPC(s.out.ensure(ctx->stream, need));
     HIPC(ctx->denoiseStage.stage(rgba, need));
     HIPC(hipMemcpyAsync(s.out.mem.p, ctx->denoiseStage.host, need, hipMemcpyHostToDevice, ctx->stream));

@@ -167,8 +167,7 @@ static int32_t dev_UseTemporalAsDenoised(dev_ctx* ctx, int32_t slot)
     HIPC(hipSetDevice(ctx->device));
     FLUSH_KEEP();
     const size_t N = (size_t)ctx->W * ctx->H;
-    DenoiseSlot& s = FrameProducts::slot(ctx->products.denoise, ctx->ringSize, slot);
-    s.valid = false; s.iterations = 0;
+    DenoiseSlot& s = denoise_slot_invalidated(ctx, slot);
     HIPC(s.out.ensure(ctx->stream, N * 16));
     hipLaunchKernelGGL(k_temporal_to_denoised, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, ctx->stream, t->temporal.as<const float4>(), (uint32_t)N, s.out.as<float4>());
     HIPC(hipGetLastError());

@@ -2,7 +2,8 @@
 // reference (its denoiser is OIDN on the host); part of the single translation unit idkpt.hip.
 //
 // The arithmetic of one written pixel lives in denoise_texel.hpp (host- and device-clean; a host build of it is compared with tests/denoise_ref.py bit for bit).  The
-// kernels below only decide which thread computes which pixel and where its 25 taps come from.  A pixel reads 25 x 48 bytes (colour, albedo, normal) and writes 16; the
+// kernels below only decide which thread computes which pixel and where its 25 taps come from; the pixel mapping, the staging loop and the clamp of a staged slot
+// (tile_pixel, stage_tile, lds_slot) are stated here once for the three filters.  A pixel reads 25 x 48 bytes (colour, albedo, normal) and writes 16; the
 // compulsory traffic is 48 + 16 bytes, so the work is in the staging:
 //  * k_denoise_tile<S> (tap spacing S = 1, 2, 4): a workgroup writes a 16 x 16 tile and first stages the (16 + 4 S)^2 texels its taps can touch — 20^2, 24^2, 32^2 — in LDS
 //    as three float4 planes with a row pitch of 32 texels (a ds_read_b128's 16-lane groups then fall on distinct slots): 30, 36 and 48 KB.  A staged texel outside the
@@ -27,6 +28,24 @@ struct Params {
 
 __device__ inline denoiset::V3 rgb(float4 q) { return denoiset::v3(q.x, q.y, q.z); }
 
+// ---- what the kernels of the three filters share (kernels_denoise_variance.hpp, kernels_denoise_temporal.hpp): grid (ceil(W / 16), ceil(H / 16)), 256 threads
+// the pixel thread t writes, (16 bx + t % 16, 16 by + t / 16); false where the image has no such pixel
+__device__ inline bool tile_pixel(int W, int H, int* x, int* y) { *x = (int)blockIdx.x * TILE + ((int)threadIdx.x & (TILE - 1)); *y = (int)blockIdx.y * TILE + ((int)threadIdx.x >> 4); return *x < W && *y < H; }
+// The staging loop over the T x T texels from (ox, oy) on, the tile and its halo: put(i, k) does the kernel's loads and stores for each one inside the image, i its index
+// in the image, k its slot in a plane of PITCH texels per row.  A texel outside the image is left unwritten.  The kernel's __syncthreads() follows the call.
+template <int T, class Put>
+__device__ inline void stage_tile(int W, int H, int ox, int oy, const Put& put)
+{
+    static_assert(T > TILE && T <= PITCH, "the staged tile must fit its pitch");
+    for (int k = (int)threadIdx.x; k < T * T; k += 256) {
+        const int ty = k / T, tx = k - ty * T, gx = ox + tx, gy = oy + ty;
+        if (gx < 0 || gx >= W || gy < 0 || gy >= H) continue;
+        put((size_t)gy * (size_t)W + (size_t)gx, ty * PITCH + tx);
+    }
+}
+// the slot of image texel (x, y) in a staged tile of `size` texels per side whose slot 0 is texel (ox, oy); clamped: no value reaches outside the planes
+__device__ inline int lds_slot(int x, int y, int ox, int oy, int size) { return min(max(y - oy, 0), size - 1) * PITCH + min(max(x - ox, 0), size - 1); }
+
 struct MemFetch {                 // colour, albedo, normal from memory: three 16-byte loads per texel
     const float4* c; const float4* a; const float4* n; int W; bool demod;
     __device__ inline void operator()(int x, int y, denoiset::V3* oc, denoiset::V3* oa, denoiset::V3* on) const
@@ -41,7 +60,7 @@ struct LdsFetch {                 // the staged tile: texel (x, y) of the image 
     const float4* c; const float4* a; const float4* n; int ox, oy, size;
     __device__ inline void operator()(int x, int y, denoiset::V3* oc, denoiset::V3* oa, denoiset::V3* on) const
     {
-        const int ix = min(max(x - ox, 0), size - 1), iy = min(max(y - oy, 0), size - 1), k = iy * PITCH + ix;
+        const int k = lds_slot(x, y, ox, oy, size);
         *oc = rgb(c[k]); *oa = rgb(a[k]); *on = rgb(n[k]);
     }
 };
@@ -55,26 +74,20 @@ __device__ inline void store_pixel(float4* __restrict__ dst, const float4* __res
 
 }  // namespace denoisek
 
-// grid (ceil(W / 16), ceil(H / 16)), 256 threads: thread t writes pixel (16 bx + t % 16, 16 by + t / 16)
 template <int S>
 __global__ __launch_bounds__(256) void k_denoise_tile(const float4* __restrict__ colour, const float4* __restrict__ albedo, const float4* __restrict__ normal, float4* __restrict__ dst, denoisek::Params p)
 {
     using namespace denoisek;
-    static_assert(S >= 1 && S <= MAX_TILE_SPACING && TILE + 4 * S <= PITCH, "the staged tile must fit its pitch");
     constexpr int T = TILE + 4 * S;
     __shared__ float4 tc[T * PITCH], ta[T * PITCH], tn[T * PITCH];
-    const int tid = (int)threadIdx.x, ox = (int)blockIdx.x * TILE - 2 * S, oy = (int)blockIdx.y * TILE - 2 * S;
-    for (int k = tid; k < T * T; k += 256) {
-        const int ty = k / T, tx = k - ty * T, gx = ox + tx, gy = oy + ty;
-        if (gx < 0 || gx >= p.W || gy < 0 || gy >= p.H) continue;
-        const size_t i = (size_t)gy * (size_t)p.W + (size_t)gx;
+    const int ox = (int)blockIdx.x * TILE - 2 * S, oy = (int)blockIdx.y * TILE - 2 * S;
+    stage_tile<T>(p.W, p.H, ox, oy, [&](size_t i, int k) {
         const float4 c = colour[i], a = albedo[i];
         const denoiset::V3 col = p.demodIn ? denoiset::demodulate(rgb(c), rgb(a)) : rgb(c);
-        tc[ty * PITCH + tx] = make_float4(col.x, col.y, col.z, 1.0f); ta[ty * PITCH + tx] = a; tn[ty * PITCH + tx] = normal[i];
-    }
+        tc[k] = make_float4(col.x, col.y, col.z, 1.0f); ta[k] = a; tn[k] = normal[i];
+    });
     __syncthreads();
-    const int x = (int)blockIdx.x * TILE + (tid & (TILE - 1)), y = (int)blockIdx.y * TILE + (tid >> 4);
-    if (x >= p.W || y >= p.H) return;
+    int x, y; if (!tile_pixel(p.W, p.H, &x, &y)) return;
     const LdsFetch f = {tc, ta, tn, ox, oy, T};
     store_pixel(dst, albedo, p, x, y, denoiset::atrous_texel(f, p.W, p.H, x, y, S, p.invC, p.invA, p.invN));
 }
@@ -83,8 +96,7 @@ __global__ __launch_bounds__(256) void k_denoise_tile(const float4* __restrict__
 __global__ __launch_bounds__(256) void k_denoise_direct(const float4* __restrict__ colour, const float4* __restrict__ albedo, const float4* __restrict__ normal, float4* __restrict__ dst, denoisek::Params p)
 {
     using namespace denoisek;
-    const int x = (int)blockIdx.x * TILE + ((int)threadIdx.x & (TILE - 1)), y = (int)blockIdx.y * TILE + ((int)threadIdx.x >> 4);
-    if (x >= p.W || y >= p.H) return;
+    int x, y; if (!tile_pixel(p.W, p.H, &x, &y)) return;
     const MemFetch f = {colour, albedo, normal, p.W, p.demodIn != 0};
     store_pixel(dst, albedo, p, x, y, denoiset::atrous_texel(f, p.W, p.H, x, y, p.s, p.invC, p.invA, p.invN));
 }

@@ -2,7 +2,7 @@
 // iterations of kernels_denoise_variance.hpp then read with first = 0.  No counterpart in the reference; part of the single translation unit idkpt.hip.
 //
 // The arithmetic of one written pixel lives in denoise_temporal_texel.hpp (host- and device-clean; a host build of it is compared with tests/denoise_temporal_ref.py bit
-// for bit).  k_temporal_state only decides which thread computes which pixel and where the 49 taps of the spatial estimate come from — the shape of k_denoise_var_tile<S>:
+// for bit).  k_temporal_state only decides which thread computes which pixel and where the 49 taps of the spatial estimate come from — the shape of k_denoise_var_tile<S>, on kernels_denoise.hpp's stage_tile:
 // a workgroup writes a 16 x 16 tile and first stages the (16 + 6)^2 texels of temporal moments, albedo and normal its taps can touch in LDS as three float4 planes with a
 // row pitch of 32 texels (33 KB).  A staged texel outside the image is left unwritten and never read (the texel function skips by the IMAGE bounds).  The temporal rgb
 // is read by its own pixel alone and goes from memory straight into the stored state.  Only pixels whose count is below SpatialBelow walk the 49 taps; the others cost a
@@ -18,7 +18,6 @@ using denoisek::PITCH;
 using denoisek::rgb;
 
 constexpr int T = TILE + 2 * denoisett::RADIUS;      // texels per side of the staged tile
-static_assert(T <= PITCH, "the staged tile must fit its pitch");
 
 struct Params {
     int W, H;
@@ -30,7 +29,7 @@ struct LdsFetch {                 // the staged tile: texel (x, y) of the image 
     const float4* m; const float4* a; const float4* n; int ox, oy;
     __device__ inline void operator()(int x, int y, denoiset::V3* om, denoiset::V3* oa, denoiset::V3* on) const
     {
-        const int k = min(max(y - oy, 0), T - 1) * PITCH + min(max(x - ox, 0), T - 1);
+        const int k = denoisek::lds_slot(x, y, ox, oy, T);
         const float4 q = m[k];
         *om = denoiset::v3(q.x, q.y, q.w); *oa = rgb(a[k]); *on = rgb(n[k]);
     }
@@ -38,21 +37,15 @@ struct LdsFetch {                 // the staged tile: texel (x, y) of the image 
 
 }  // namespace denoisetk
 
-// grid (ceil(W / 16), ceil(H / 16)), 256 threads: thread t writes pixel (16 bx + t % 16, 16 by + t / 16) of dst = (c0.rgb, v0)
+// dst = (c0.rgb, v0)
 __global__ __launch_bounds__(256) void k_temporal_state(const float4* __restrict__ temporal, const float4* __restrict__ moments, const float4* __restrict__ albedo, const float4* __restrict__ normal, float4* __restrict__ dst, denoisetk::Params p)
 {
     using namespace denoisetk;
     __shared__ float4 tm[T * PITCH], ta[T * PITCH], tn[T * PITCH];
-    const int tid = (int)threadIdx.x, ox = (int)blockIdx.x * TILE - denoisett::RADIUS, oy = (int)blockIdx.y * TILE - denoisett::RADIUS;
-    for (int k = tid; k < T * T; k += 256) {
-        const int ty = k / T, tx = k - ty * T, gx = ox + tx, gy = oy + ty;
-        if (gx < 0 || gx >= p.W || gy < 0 || gy >= p.H) continue;
-        const size_t i = (size_t)gy * (size_t)p.W + (size_t)gx;
-        tm[ty * PITCH + tx] = moments[i]; ta[ty * PITCH + tx] = albedo[i]; tn[ty * PITCH + tx] = normal[i];
-    }
+    const int ox = (int)blockIdx.x * TILE - denoisett::RADIUS, oy = (int)blockIdx.y * TILE - denoisett::RADIUS;
+    denoisek::stage_tile<T>(p.W, p.H, ox, oy, [&](size_t i, int k) { tm[k] = moments[i]; ta[k] = albedo[i]; tn[k] = normal[i]; });
     __syncthreads();
-    const int x = (int)blockIdx.x * TILE + (tid & (TILE - 1)), y = (int)blockIdx.y * TILE + (tid >> 4);
-    if (x >= p.W || y >= p.H) return;
+    int x, y; if (!denoisek::tile_pixel(p.W, p.H, &x, &y)) return;
     const LdsFetch f = {tm, ta, tn, ox, oy};
     const size_t i = (size_t)y * (size_t)p.W + (size_t)x;
     const denoisevt::State st = denoisett::temporal_state(f, p.W, p.H, x, y, rgb(temporal[i]), p.spatialBelow, p.invA, p.invN, p.demod != 0);

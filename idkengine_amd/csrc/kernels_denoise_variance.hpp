@@ -3,7 +3,7 @@
 //
 // The arithmetic of one written pixel lives in denoise_variance_texel.hpp (host- and device-clean; a host build of it is compared with tests/denoise_variance_ref.py bit
 // for bit).  The kernels below only decide which thread computes which pixel and where its 25 taps and the 9 variances of the prefilter come from — the shape of
-// kernels_denoise.hpp:
+// kernels_denoise.hpp, whose tile_pixel, stage_tile and lds_slot they use:
 //  * k_denoise_var_tile<S> (tap spacing S = 1, 2, 4): a workgroup writes a 16 x 16 tile and first stages the (16 + 4 S)^2 texels its taps can touch in LDS as three float4
 //    planes with a row pitch of 32 texels; the variance rides in the colour plane's .w, so the footprint is k_denoise_tile<S>'s (30, 36, 48 KB).  The prefilter reads
 //    p +- 1, inside the halo because 2 S >= 2.  A staged texel outside the image is left unwritten and never read (the texel function skips by the IMAGE bounds).
@@ -40,7 +40,7 @@ struct MemFetch {                 // state, albedo, normal from memory: three 16
 };
 struct LdsFetch {                 // the staged tile: texel (x, y) of the image is slot (x - ox, y - oy)
     const float4* c; const float4* a; const float4* n; int ox, oy, size;
-    __device__ inline int slot(int x, int y) const { return min(max(y - oy, 0), size - 1) * PITCH + min(max(x - ox, 0), size - 1); }
+    __device__ inline int slot(int x, int y) const { return denoisek::lds_slot(x, y, ox, oy, size); }
     __device__ inline void operator()(int x, int y, denoisevt::State* os, denoiset::V3* oa, denoiset::V3* on) const
     {
         const int k = slot(x, y);
@@ -61,31 +61,25 @@ __device__ inline void store_pixel(float4* __restrict__ dst, const float4* __res
 
 }  // namespace denoisevk
 
-// grid (ceil(W / 16), ceil(H / 16)), 256 threads: thread t writes pixel (16 bx + t % 16, 16 by + t / 16).  `state` is Result when p.first (then `moments` is read as
-// well; S == 1), else the previous iteration's (c.rgb, v) image.
+// `state` is Result when p.first (then `moments` is read as well; S == 1), else the previous iteration's (c.rgb, v) image.
 template <int S>
 __global__ __launch_bounds__(256) void k_denoise_var_tile(const float4* __restrict__ state, const float4* __restrict__ moments, const float4* __restrict__ albedo, const float4* __restrict__ normal, float4* __restrict__ dst, denoisevk::Params p)
 {
     using namespace denoisevk;
-    static_assert(S >= 1 && S <= denoisek::MAX_TILE_SPACING && TILE + 4 * S <= PITCH, "the staged tile must fit its pitch");
     constexpr int T = TILE + 4 * S;
     __shared__ float4 tc[T * PITCH], ta[T * PITCH], tn[T * PITCH];
-    const int tid = (int)threadIdx.x, ox = (int)blockIdx.x * TILE - 2 * S, oy = (int)blockIdx.y * TILE - 2 * S;
-    for (int k = tid; k < T * T; k += 256) {
-        const int ty = k / T, tx = k - ty * T, gx = ox + tx, gy = oy + ty;
-        if (gx < 0 || gx >= p.W || gy < 0 || gy >= p.H) continue;
-        const size_t i = (size_t)gy * (size_t)p.W + (size_t)gx;
+    const int ox = (int)blockIdx.x * TILE - 2 * S, oy = (int)blockIdx.y * TILE - 2 * S;
+    denoisek::stage_tile<T>(p.W, p.H, ox, oy, [&](size_t i, int k) {
         float4 c = state[i]; const float4 a = albedo[i];
         if (S == 1 && p.first) {
             const float4 m = moments[i];
             const denoisevt::State st = denoisevt::first_state(rgb(c), m.x, m.y, p.n, rgb(a), p.demod != 0);
             c = make_float4(st.c.x, st.c.y, st.c.z, st.v);
         }
-        tc[ty * PITCH + tx] = c; ta[ty * PITCH + tx] = a; tn[ty * PITCH + tx] = normal[i];
-    }
+        tc[k] = c; ta[k] = a; tn[k] = normal[i];
+    });
     __syncthreads();
-    const int x = (int)blockIdx.x * TILE + (tid & (TILE - 1)), y = (int)blockIdx.y * TILE + (tid >> 4);
-    if (x >= p.W || y >= p.H) return;
+    int x, y; if (!denoisek::tile_pixel(p.W, p.H, &x, &y)) return;
     const LdsFetch f = {tc, ta, tn, ox, oy, T};
     store_pixel(dst, albedo, p, x, y, denoisevt::atrous_variance_texel(f, p.W, p.H, x, y, S, p.ls2, p.eps, p.invA, p.invN));
 }
@@ -94,8 +88,7 @@ __global__ __launch_bounds__(256) void k_denoise_var_tile(const float4* __restri
 __global__ __launch_bounds__(256) void k_denoise_var_direct(const float4* __restrict__ state, const float4* __restrict__ albedo, const float4* __restrict__ normal, float4* __restrict__ dst, denoisevk::Params p)
 {
     using namespace denoisevk;
-    const int x = (int)blockIdx.x * TILE + ((int)threadIdx.x & (TILE - 1)), y = (int)blockIdx.y * TILE + ((int)threadIdx.x >> 4);
-    if (x >= p.W || y >= p.H) return;
+    int x, y; if (!denoisek::tile_pixel(p.W, p.H, &x, &y)) return;
     const MemFetch f = {state, albedo, normal, p.W};
     store_pixel(dst, albedo, p, x, y, denoisevt::atrous_variance_texel(f, p.W, p.H, x, y, p.s, p.ls2, p.eps, p.invA, p.invN));
 }

@@ -12,6 +12,7 @@
 #include <string.h>
 #include <vector>
 #include "../../idkengine_amd/csrc/denoise_temporal_texel.hpp"
+#include "denoise_state_host.hpp"
 #include "../../idkengine_amd/csrc/reproject_texel.hpp"
 
 using denoiset::V3;
@@ -19,17 +20,6 @@ using denoiset::v3;
 using denoisevt::State;
 
 static bool read_all(FILE* f, void* p, size_t bytes) { return fread(p, 1, bytes, f) == bytes; }
-
-struct StateFetch {                      // as kernels_denoise_variance.hpp MemFetch: the state image holds (c.rgb, v)
-    const float* c; const float* a; const float* n; int W;
-    void operator()(int x, int y, State* os, V3* oa, V3* on) const
-    {
-        const size_t i = ((size_t)y * (size_t)W + (size_t)x) * 4;
-        os->c = v3(c[i], c[i + 1], c[i + 2]); os->v = c[i + 3];
-        *oa = v3(a[i], a[i + 1], a[i + 2]); *on = v3(n[i], n[i + 1], n[i + 2]);
-    }
-    float variance(int x, int y) const { return c[((size_t)y * (size_t)W + (size_t)x) * 4 + 3]; }
-};
 
 struct MomentsFetch {                    // as kernels_denoise_temporal.hpp LdsFetch: (M1, M2, cnt) are channels x, y, w.  Aborts on a texel outside the image
     const float* m; const float* a; const float* n; int W, H;
@@ -62,7 +52,7 @@ static int run_filter(FILE* in, FILE* out)
     if (!read_all(in, temporal.data(), N * 4) || !read_all(in, moments.data(), N * 4) || !read_all(in, albedo.data(), N * 4) || !read_all(in, normal.data(), N * 4)) { fprintf(stderr, "short images\n"); return 1; }
     const float ls2 = sig[0] * sig[0], eps = sig[1], invA = denoiset::inv_sigma2(sig[2], 0), invN = denoiset::inv_sigma2(sig[3], 0), spatialBelow = sig[4];
 
-    // the pre-pass into ping[1], iteration i into ping[i & 1]
+    // the pre-pass into ping[1], iteration i into ping[i & 1] (denoise_state_host.hpp)
     std::vector<float> ping[2] = {std::vector<float>(N), std::vector<float>(N)};
     const MomentsFetch mf = {moments.data(), albedo.data(), normal.data(), W, H};
     for (int y = 0; y < H; y++) for (int x = 0; x < W; x++) {
@@ -70,21 +60,7 @@ static int run_filter(FILE* in, FILE* out)
         const State st = denoisett::temporal_state(mf, W, H, x, y, v3(temporal[k], temporal[k + 1], temporal[k + 2]), spatialBelow, invA, invN, demod != 0);
         ping[1][k] = st.c.x; ping[1][k + 1] = st.c.y; ping[1][k + 2] = st.c.z; ping[1][k + 3] = st.v;
     }
-    const float* src = ping[1].data();
-    for (int i = 0; i < iterations; i++) {
-        std::vector<float>& dst = ping[i & 1];
-        const StateFetch f = {src, albedo.data(), normal.data(), W};
-        for (int y = 0; y < H; y++) for (int x = 0; x < W; x++) {
-            State r = denoisevt::atrous_variance_texel(f, W, H, x, y, 1 << i, ls2, eps, invA, invN);
-            const size_t k = ((size_t)y * W + x) * 4;
-            if (i == iterations - 1) {
-                if (demod) r.c = denoiset::remodulate(r.c, v3(albedo[k], albedo[k + 1], albedo[k + 2]));
-                r.v = 1.0f;
-            }
-            dst[k] = r.c.x; dst[k + 1] = r.c.y; dst[k + 2] = r.c.z; dst[k + 3] = r.v;
-        }
-        src = dst.data();
-    }
+    const float* src = variance_iterations(ping[1].data(), ping, albedo.data(), normal.data(), W, H, iterations, demod, ls2, eps, invA, invN);
     fwrite(src, 4, N, out);
     return 0;
 }

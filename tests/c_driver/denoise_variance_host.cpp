@@ -1,6 +1,6 @@
 // denoise_variance_host.cpp — the per-pixel functions of idkengine_amd/csrc/denoise_variance_texel.hpp (what the device kernels of kernels_denoise_variance.hpp call)
-// compiled for the HOST and run over a whole frame the way host_denoise_variance.hpp runs the launches: tests/test_denoise_variance_ref.py builds this with
-// g++ -ffp-contract=off -fsanitize=address,undefined and compares the image with tests/denoise_variance_ref.py's binary32 restatement bit for bit.
+// compiled for the HOST and run over a whole frame the way host_denoise_variance.hpp runs the launches (the iterations: denoise_state_host.hpp):
+// tests/test_denoise_variance_ref.py builds this with g++ -ffp-contract=off -fsanitize=address,undefined and compares the image with tests/denoise_variance_ref.py's binary32 restatement bit for bit.
 //   denoise_variance_host IN OUT
 // IN:  int32 W, H, Iterations, DemodulateAlbedo, N; float LumaSigma, VarianceEpsilon, AlbedoSigma, NormalSigma; then Result, Albedo, Normal, Moments: W * H * 4 floats each.
 // OUT: W * H * 4 floats (rgb, 1.0).
@@ -8,20 +8,9 @@
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
-#include "../../idkengine_amd/csrc/denoise_variance_texel.hpp"
+#include "denoise_state_host.hpp"
 
 using namespace denoisevt;
-
-struct HostFetch {                       // as kernels_denoise_variance.hpp MemFetch: the state image holds (c.rgb, v)
-    const float* c; const float* a; const float* n; int W;
-    void operator()(int x, int y, State* os, V3* oa, V3* on) const
-    {
-        const size_t i = ((size_t)y * (size_t)W + (size_t)x) * 4;
-        os->c = v3(c[i], c[i + 1], c[i + 2]); os->v = c[i + 3];
-        *oa = v3(a[i], a[i + 1], a[i + 2]); *on = v3(n[i], n[i + 1], n[i + 2]);
-    }
-    float variance(int x, int y) const { return c[((size_t)y * (size_t)W + (size_t)x) * 4 + 3]; }
-};
 
 int main(int argc, char** argv)
 {
@@ -44,21 +33,7 @@ int main(int argc, char** argv)
         first[k] = st.c.x; first[k + 1] = st.c.y; first[k + 2] = st.c.z; first[k + 3] = st.v;
     }
     const float ls2 = sig[0] * sig[0], eps = sig[1], invA = denoiset::inv_sigma2(sig[2], 0), invN = denoiset::inv_sigma2(sig[3], 0);
-    const float* src = first.data();
-    for (int i = 0; i < iterations; i++) {
-        std::vector<float>& dst = ping[i & 1];
-        const HostFetch f = {src, albedo.data(), normal.data(), W};
-        for (int y = 0; y < H; y++) for (int x = 0; x < W; x++) {
-            State r = atrous_variance_texel(f, W, H, x, y, 1 << i, ls2, eps, invA, invN);
-            const size_t k = ((size_t)y * W + x) * 4;
-            if (i == iterations - 1) {
-                if (demod) r.c = denoiset::remodulate(r.c, v3(albedo[k], albedo[k + 1], albedo[k + 2]));
-                r.v = 1.0f;
-            }
-            dst[k] = r.c.x; dst[k + 1] = r.c.y; dst[k + 2] = r.c.z; dst[k + 3] = r.v;
-        }
-        src = dst.data();
-    }
+    const float* src = variance_iterations(first.data(), ping, albedo.data(), normal.data(), W, H, iterations, demod, ls2, eps, invA, invN);
     FILE* o = fopen(argv[2], "wb");
     if (!o) { perror(argv[2]); return 1; }
     fwrite(src, 4, N, o);

@@ -264,6 +264,55 @@ def test_with_a_uniform_integer_count_the_filter_is_denoise_variance(scene):
     pt.Dispose()
 
 
+def test_the_fillers_in_any_order_on_one_slot(scene):
+    """Every call that fills the denoised image of a slot, one behind the other on ONE slot, so that each meets the ping images a different filler left present or absent
+    (idkptDenoise and idkptDenoiseVariance make ping[0] from 2 iterations and ping[1] from 3, idkptDenoiseTemporal ping[1] always and ping[0] from 2, idkptUploadDenoised
+    neither): each image is its own restatement's bit for bit, idkptGetDenoiseRoute answers for exactly that call's iterations, and no guard is touched."""
+    W, H, N = 37, 23, 2
+    pt = started(scene, W, H, samples=N)
+    assert pt.AccumulatedSamples == N
+    result, _, _, moments = V.random_images(W, H, N=N)
+    temporal, tm, albedo, normal = R.random_images(W, H)
+    write_ptr(pt, pt.frame_device_ptr(0, 0), result); write_ptr(pt, pt.moments_device_ptr(0), moments)
+    plant_filter_inputs(pt, (temporal, tm, albedo, normal), 0)
+    uploaded = np.random.default_rng(5).random((H, W, 4)).astype(F)
+
+    def plain(it, demod):
+        s = D.settings(it, demod); d = T.Denoise(**s)
+        pt._check(pt._L.idkptDenoise(pt._ctx, 0, C.addressof(d)))
+        return D.denoise(result, albedo, normal, **s), it
+
+    def variance(it, demod):
+        s = V.settings(it, demod); d = T.DenoiseVariance(**s)
+        pt._check(pt._L.idkptDenoiseVariance(pt._ctx, 0, C.addressof(d)))
+        return V.denoise_variance(result, albedo, normal, moments, N, **s), it
+
+    def temporal_filter(it, demod):
+        s = R.settings(it, demod)
+        pt._check(c_temporal(pt, s, 0))
+        return R.denoise_temporal(temporal, tm, albedo, normal, **s), it
+
+    def upload():
+        pt.UploadDenoised(uploaded, 0)
+        return uploaded, 0
+
+    steps = [("Denoise 1", lambda: plain(1, 1)), ("DenoiseTemporal 1", lambda: temporal_filter(1, 0)), ("DenoiseVariance 2", lambda: variance(2, 1)), ("Denoise 3", lambda: plain(3, 0)),
+             ("UploadDenoised", upload), ("DenoiseTemporal 2", lambda: temporal_filter(2, 1)), ("DenoiseVariance 1", lambda: variance(1, 0))]
+    r = C.c_int32()
+    for name, step in steps:
+        want, it = step()
+        got, guard = denoised_and_guard(pt, 0)
+        assert R.same(got, want), (name, differing(got, want))
+        assert (guard == 0xA5).all(), name
+        assert [pt.denoise_route(i, 0) for i in range(it)] == [R.route(i) for i in range(it)], name
+        assert pt._L.idkptGetDenoiseRoute(pt._ctx, 0, it, C.byref(r)) == INVALID_ARGUMENT, name      # exactly that call's iterations: none past them
+        assert guards_intact(pt, (0,)), name
+    # the inputs are read, not written
+    assert R.same(pt.FrameResult(0, 0), result) and R.same(pt.DownloadMoments(0), moments) and R.same(pt.DownloadTemporal(0), temporal) and R.same(pt.DownloadTemporalMoments(0), tm)
+    assert R.same(pt.FrameResult(0, 1), albedo) and R.same(pt.FrameResult(0, 2), normal)
+    pt.Dispose()
+
+
 # ---- 5. end to end: eight one-sample frames along a camera path
 def path_camera(W, H, k, frames=8):
     a, b = CAM_A, CAMS_B["rotation"]                     # about 1.4 pixels per frame: new columns enter every frame, so counts below SpatialBelow exist in every frame
