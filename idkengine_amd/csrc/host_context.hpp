@@ -133,6 +133,40 @@ struct FrameProducts {
     template <class S> static S& slot(std::vector<S>& v, int ringSize, int slot) { if (v.size() != (size_t)ringSize) { drop(v); v.resize(ringSize); } return v[slot]; }
 };
 
+// ---- derived scene structures --------------------------------------------------------------------------------------------------------------------------
+// What the library derives on the device from what the host uploads — the paired node layout, the 4-wide nodes, the instance records, the triangle marks, the chunk table, its own
+// TLAS, the unified tree / general array — with the measured decisions that ride on them and the packet walk's probing state.  Which write makes which of them stale is
+// derived_scene.hpp's table and nothing else: every write says its Cause to invalidate(), every derivation (host_derived.hpp, lazily in front of the batch that needs it) marks what
+// it made.  The buffers only grow: invalidation frees nothing, idkptDestroy releases them.  To add a structure: a bit, its entry in the row of every cause, a *_prepare, a line in release().
+#include "derived_scene.hpp"
+// 64 bytes of host memory the device writes through `dev` (a kernel's counters, a build's measurements): mapped and zeroed at first use
+struct MappedWords {
+    void* host = nullptr; void* dev = nullptr;
+    hipError_t ensure() { if (host) return hipSuccess; hipError_t e = hipHostMalloc(&host, 64, hipHostMallocMapped); if (e != hipSuccess) { host = nullptr; return e; } memset(host, 0, 64); return hipHostGetDevicePointer(&dev, host, 0); }
+    void release() { if (host) (void)hipHostFree(host); host = nullptr; dev = nullptr; }
+    template <class T> T* host_as() const { return (T*)host; }
+    template <class T> T* dev_as() const { return (T*)dev; }
+};
+struct DerivedScene : derived::State {
+    DevBuf wnodes, wleaf, wids, wpair, wcounts; std::vector<uint32_t> wNodeOff, wLeafOff;   // wide nodes (kernels_wide.hpp), per BLAS from nodes + triVerts.  WIDE_TOPO: the children lists match the node topology; WIDE_FILL: boxes / leaf records match the current boxes and positions
+    DevBuf pairNodes;                                     // DScene::pairNodes (k_pair_nodes): re-derived after everything that changes node boxes or topology
+    DevBuf instRec;                                       // DScene::instRec (k_inst_records): one scene version only; re-derived with the own TLAS's triggers
+    // the library's own TLAS for the instance loop (kernels_trace_inst.hpp): padded PLOC tree over the instances, and the per-triangle "not contained in its leaf box" marks;
+    // both derived on the device before the first batch that wants them and after everything that moves boxes, positions or transforms
+    DevBuf itlas, imarks, ichunks; int itlasNeed = 1; uint32_t ichunkCount = 0;
+    DevBuf entRec, braidBuf; bool itlasBraided = false; int itlasDepth = 0, itlasEntries = 0;   // k_braid's entry records / (entries, areas, leaf boxes, count); the built tree's depth and leaf count as last read from the device (0: not known)
+    MappedWords overlap; bool isieveWorth = false;        // host-mapped: instance boxes a random line meets, the leaves, the built tree's depth (k_tlas_build)
+    int uniMode = 0; uint32_t uniBaseB = 0, uniRestoreIdx = 0;   // uniMode: 1 = the unified tree of a same-space scene (TREE 1), 2 = the general array (TREE 2: world-space top, entries switch spaces)
+    DevBuf unodes, utlas, uTabs, uniBuf, uniEntRec; bool uniEligible = false; int uniCap = 0, uniEntries = 0, uniDepth = 0; MappedWords uni;   // the unified tree (k_unify_*): nodes, its PLOC top, the per-BLAS tables; host-mapped: [1] entries, [2] depth of the top
+    // the packet walk's counters arrive through host-mapped memory one or two batches late (k_packet_mirror): [1] packets, [2] node steps, [3] live lanes, [4] rays entered, [5] triangle rounds — totals since the last reset
+    MappedWords pkStats; unsigned long long pkSeen[6] = {0, 0, 0, 0, 0, 0}; float pkCam[36] = {0}; int pkW = 0, pkRows = 0, pkBatch = 0; float pkLastLive = -1.0f;
+    void release()
+    {
+        for (DevBuf* b : {&wnodes, &wleaf, &wids, &wpair, &wcounts, &pairNodes, &instRec, &itlas, &imarks, &ichunks, &entRec, &braidBuf, &unodes, &utlas, &uTabs, &uniBuf, &uniEntRec}) b->release();
+        overlap.release(); uni.release(); pkStats.release(); valid = 0;
+    }
+};
+
 // Tuning / test options (idkptSetDeveloperOption; none is part of the reference's interface and results are bit-identical under all of them:
 // tests/test_gpu_worklist.py, test_gpu_layout.py).  The library itself never reads the environment; the Python host mirror forwards IDKPT_<NAME>.
 struct DevOptions {
@@ -256,21 +290,9 @@ struct dev_ctx {
     std::vector<uint32_t> unskinnedMaxJoint, unskinnedBlockMaxJoint;   // per unskinned vertex the largest of its four JointIndices, and the maxima of blocks of 256 vertices: idkptSkin's joint-table check without a scan per frame
     int sceneStack = 1;
     int hInst0Blas = 0;                              // BlasId of instance 0 (MODE 0 traverses that BLAS)
-    // wide nodes (kernels_wide.hpp): derived per BLAS from nodes + triVerts.  wideTopoValid: the children lists match the node topology; wideFillValid: boxes / leaf records match the current boxes and positions
-    DevBuf wnodes, wleaf, wids, wpair, wcounts, wtotals; std::vector<uint32_t> wNodeOff, wLeafOff; bool wideTopoValid = false, wideFillValid = false;
-    // the library's own TLAS for the instance loop (kernels_trace_inst.hpp): padded PLOC tree over the instances, and the per-triangle "not contained in its leaf box" marks;
-    // both derived on the device before the first batch that wants them and after everything that moves boxes, positions or transforms
-    DevBuf pairNodes; bool pairValid = false;             // DScene::pairNodes (k_pair_nodes): re-derived after everything that changes node boxes or topology
-    DevBuf instRec; bool instRecValid = false;            // DScene::instRec (k_inst_records): one scene version only; re-derived with the own TLAS's triggers
-    DevBuf itlas, imarks, ichunks; int itlasNeed = 1; uint32_t ichunkCount = 0; bool itlasValid = false, imarksValid = false;
-    int uniMode = 0; uint32_t uniBaseB = 0, uniRestoreIdx = 0;   // uniMode: 1 = the unified tree of a same-space scene (TREE 1), 2 = the general array (TREE 2: world-space top, entries switch spaces)
-    DevBuf unodes, utlas, uTabs, uniBuf, uniEntRec; bool uniValid = false, uniEligible = false, uniTabsValid = false; int uniCap = 0, uniEntries = 0, uniDepth = 0; float* hUni = nullptr; float* dUni = nullptr;   // the unified tree (k_unify_*): nodes, its PLOC top, the per-BLAS tables; host-mapped: [1] entries, [2] depth of the top
+    DerivedScene derived;                            // everything derived on the device from the uploaded scene, and what of it is stale (derived_scene.hpp)
+    DevBuf wtotals;                                  // totals of the optional walks since idkptResetStats (host_derived.hpp totals_ensure)
     std::vector<GpuBlasInstance> hInstances; std::vector<char> hXforms; uint64_t uniLaunches = 0;   // host copies of the instance list and of the GpuMeshTransforms as last uploaded / patched
-    DevBuf entRec, braidBuf; bool itlasBraided = false; int itlasDepth = 0, itlasEntries = 0;   // k_braid's entry records / (entries, areas, leaf boxes, count); the built tree's depth and leaf count as last read from the device (0: not known)
-    // the packet walk's decision (host_launch.hpp packet_decide): 0 = probing (packets on, counters awaited), 1 = on, 2 = off; the kernel's counters arrive through host-mapped memory
-    // one or two batches late (k_packet_mirror): [1] packets, [2] node steps, [3] live lanes, [4] rays entered, [5] triangle rounds — totals since the last reset
-    int pkState = 0, pkBatchesSinceProbe = 0; unsigned long long* hPkStats = nullptr; unsigned long long* dPkStats = nullptr; unsigned long long pkSeen[6] = {0, 0, 0, 0, 0, 0}; float pkCam[36] = {0}; int pkW = 0, pkRows = 0, pkBatch = 0; float pkLastLive = -1.0f;
-    float* hInstOverlap = nullptr; float* dInstOverlap = nullptr; bool instOverlapKnown = false, itlasBuilt = false, isieveWorth = false;   // host-mapped: instance boxes a random line meets (k_tlas_build); known = read at least once since the upload
     // scene versions: slot count a versioned buffer may grow to, per buffer the bytes of one state / the slot pitch / the slots its arena holds / the current slot
     int verSlots = 1; size_t vbytes[VB_COUNT] = {0}, vstride[VB_COUNT] = {0}; int valloc[VB_COUNT] = {1, 1, 1, 1, 1}, vcur[VB_COUNT] = {0};
     uint64_t lastMask[VB_COUNT] = {0};               // slots the last launched batch reads (a deferred last bounce still does: finish_deferred)

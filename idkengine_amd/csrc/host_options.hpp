@@ -38,21 +38,21 @@ static int32_t dev_SetOption(dev_ctx* ctx, const char* name, int32_t value)
 #ifdef IDKPT_DEVELOPER
     else if (n == "graph_probe") o.graphProbe = std::max(0, value);
 #endif
-    else if (n == "inst_tlas_overlap") { REQUIRE(value >= 0 && value <= 100, "idkptSetDeveloperOption: inst_tlas_overlap is a percentage"); FLUSH(); o.instTlasOverlap = value; ctx->itlasValid = false; }
+    else if (n == "inst_tlas_overlap") { REQUIRE(value >= 0 && value <= 100, "idkptSetDeveloperOption: inst_tlas_overlap is a percentage"); FLUSH(); o.instTlasOverlap = value; ctx->derived.invalidate(derived::Cause::InstOption); }
     else if (n == "bounce_pixel_major") { REQUIRE(value >= 0 && value <= 2, "idkptSetDeveloperOption: bounce_pixel_major is 0..2"); o.bouncePixelMajor = value; }
     else if (n == "gen_group_max") { REQUIRE(value >= 1 && value <= 16, "idkptSetDeveloperOption: gen_group_max is 1..16"); o.genGroupMax = value; }
     else if (n == "gen_pixel_major") { REQUIRE(value >= 0, "idkptSetDeveloperOption: gen_pixel_major is >= 0"); o.genPixelMajor = value; }
-    else if (n == "inst_sieve_overlap") { REQUIRE(value >= 0 && value <= 100, "idkptSetDeveloperOption: inst_sieve_overlap is a percentage"); FLUSH(); o.instSieveOverlap = value; ctx->itlasValid = false; }
-    else if (n == "inst_sieve") { REQUIRE(value >= 0, "idkptSetDeveloperOption: inst_sieve is >= 0"); FLUSH(); o.instSieve = value; ctx->itlasValid = false; }
-    else if (n == "inst_braid") { REQUIRE(value >= 0, "idkptSetDeveloperOption: inst_braid is >= 0"); FLUSH(); o.instBraid = value; ctx->itlasValid = false; }   // (entries of the own TLAS after partial re-braiding, k_braid; 0: whole instances)
+    else if (n == "inst_sieve_overlap") { REQUIRE(value >= 0 && value <= 100, "idkptSetDeveloperOption: inst_sieve_overlap is a percentage"); FLUSH(); o.instSieveOverlap = value; ctx->derived.invalidate(derived::Cause::InstOption); }
+    else if (n == "inst_sieve") { REQUIRE(value >= 0, "idkptSetDeveloperOption: inst_sieve is >= 0"); FLUSH(); o.instSieve = value; ctx->derived.invalidate(derived::Cause::InstOption); }
+    else if (n == "inst_braid") { REQUIRE(value >= 0, "idkptSetDeveloperOption: inst_braid is >= 0"); FLUSH(); o.instBraid = value; ctx->derived.invalidate(derived::Cause::InstOption); }   // (entries of the own TLAS after partial re-braiding, k_braid; 0: whole instances)
     else if (n == "pair_nodes") { REQUIRE(value == 0 || value == 1, "idkptSetDeveloperOption: pair_nodes is 0 or 1"); o.pairNodes = value; }
-    else if (n == "inst_general") { REQUIRE(value >= 0, "idkptSetDeveloperOption: inst_general is >= 0"); FLUSH(); o.instGeneral = value; ctx->itlasValid = false; }
+    else if (n == "inst_general") { REQUIRE(value >= 0, "idkptSetDeveloperOption: inst_general is >= 0"); FLUSH(); o.instGeneral = value; ctx->derived.invalidate(derived::Cause::InstOption); }
     else if (n == "uni_refill") { REQUIRE(value == 16 || value == 32, "idkptSetDeveloperOption: uni_refill is 16 or 32"); o.uniRefill = value; }
-    else if (n == "inst_unify_radius") { REQUIRE(value >= 1 && value <= 512, "idkptSetDeveloperOption: inst_unify_radius is 1-512"); FLUSH(); o.instUnifyRadius = value; ctx->itlasValid = false; }
-    else if (n == "inst_unify") { REQUIRE(value >= 0, "idkptSetDeveloperOption: inst_unify is >= 0"); FLUSH(); o.instUnify = value; ctx->itlasValid = false; }   // (subtrees under the unified tree's top, k_unify_*; 0: off)
-    else if (n == "inst_tlas") { REQUIRE(value >= 0, "idkptSetDeveloperOption: inst_tlas is >= 0"); FLUSH(); o.instTlas = value; ctx->itlasValid = false; }   // (0: the exact instance loop only; n: the library's own TLAS from n instances on)
-    else if (n == "packet") { REQUIRE(value >= 0 && value <= 2, "idkptSetDeveloperOption: packet is 0..2"); o.packet = value; ctx->pkState = 0; ctx->pkBatchesSinceProbe = 0; }
-    else if (n == "packet_min_live") { REQUIRE(value >= 0 && value <= 100, "idkptSetDeveloperOption: packet_min_live is a percentage"); o.packetMinLive = value; ctx->pkState = 0; ctx->pkBatchesSinceProbe = 0; }
+    else if (n == "inst_unify_radius") { REQUIRE(value >= 1 && value <= 512, "idkptSetDeveloperOption: inst_unify_radius is 1-512"); FLUSH(); o.instUnifyRadius = value; ctx->derived.invalidate(derived::Cause::InstOption); }
+    else if (n == "inst_unify") { REQUIRE(value >= 0, "idkptSetDeveloperOption: inst_unify is >= 0"); FLUSH(); o.instUnify = value; ctx->derived.invalidate(derived::Cause::InstOption); }   // (subtrees under the unified tree's top, k_unify_*; 0: off)
+    else if (n == "inst_tlas") { REQUIRE(value >= 0, "idkptSetDeveloperOption: inst_tlas is >= 0"); FLUSH(); o.instTlas = value; ctx->derived.invalidate(derived::Cause::InstOption); }   // (0: the exact instance loop only; n: the library's own TLAS from n instances on)
+    else if (n == "packet") { REQUIRE(value >= 0 && value <= 2, "idkptSetDeveloperOption: packet is 0..2"); o.packet = value; ctx->derived.packet_reprobe(); }
+    else if (n == "packet_min_live") { REQUIRE(value >= 0 && value <= 100, "idkptSetDeveloperOption: packet_min_live is a percentage"); o.packetMinLive = value; ctx->derived.packet_reprobe(); }
     else if (n == "packet_waves") { REQUIRE(value >= 0 && value <= 32, "idkptSetDeveloperOption: packet_waves is 0 (default) or 1..32"); o.packetWaves = value; }
     else if (n == "wide") { REQUIRE(value >= 0 && value <= 1, "idkptSetDeveloperOption: wide is 0 or 1"); FLUSH(); o.wide = value; }
     else if (n == "wide_cap") { REQUIRE(value >= 0 && value <= 96, "idkptSetDeveloperOption: wide_cap is 0 (default) or 4..96 rows"); o.wideCap = value; }

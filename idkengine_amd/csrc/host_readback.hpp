@@ -142,7 +142,7 @@ static int32_t dev_GetStats(dev_ctx* ctx, idkpt_stats* out)
     if (ctx->wtotals.p) { uint64_t w[16]; HIPC(hipMemcpyAsync(w, ctx->wtotals.p, TOTALS_BYTES, hipMemcpyDeviceToHost, ctx->stream)); HIPC(hipStreamSynchronize(ctx->stream)); s.WideFlaggedRays = w[0]; s.WideNodeVisits = w[1]; s.WideLeafRecords = w[2]; s.WideTriangleTests = w[3]; s.InstTlasFlaggedRays = w[4];
         s.PacketFlaggedRays = w[8]; s.PacketPackets = w[9]; s.PacketNodeSteps = w[10]; s.PacketLiveLanes = w[11]; s.PacketRaysEntered = w[12]; s.PacketTriangleRounds = w[13]; }
     s.LastOcclusionLaunches = ctx->occlLaunches; s.LastFoldBatches = ctx->foldBatches;
-    s.InstUnifiedLaunches = ctx->uniLaunches; s.InstUnifiedEntries = ctx->uniValid ? (uint32_t)ctx->uniEntries : 0u; s.InstUnifiedTopDepth = ctx->uniValid ? (uint32_t)ctx->uniDepth : 0u;
+    s.InstUnifiedLaunches = ctx->uniLaunches; s.InstUnifiedEntries = ctx->derived.holds(derived::UNI) ? (uint32_t)ctx->derived.uniEntries : 0u; s.InstUnifiedTopDepth = ctx->derived.holds(derived::UNI) ? (uint32_t)ctx->derived.uniDepth : 0u;
     *out = s;
     return IDKPT_OK;
 }
@@ -154,8 +154,8 @@ static int32_t dev_ResetStats(dev_ctx* ctx)
     FLUSH_KEEP();
     HIPC(hipStreamSynchronize(ctx->stream));
     memset(&ctx->stats, 0, sizeof(ctx->stats)); ctx->uniLaunches = 0; ctx->occlLaunches = 0; ctx->foldBatches = 0;
-    if (ctx->hPkStats) memset(ctx->hPkStats, 0, 64);
-    for (int i = 0; i < 6; i++) ctx->pkSeen[i] = 0;
+    if (ctx->derived.pkStats.host) memset(ctx->derived.pkStats.host, 0, 64);
+    for (int i = 0; i < 6; i++) ctx->derived.pkSeen[i] = 0;
     ctx->evUsed = 0; ctx->traceMsAcc = 0.0; ctx->traceLaunchesAcc = 0;
     memset(ctx->hCounts, 0, (MAX_DEPTH_SLOTS - 1) * 4);     // (the last word, the length of the primary active list, is also the grid hint of the next batch: idkptGetStats reports it only once frames were rendered)
     HIPC(hipMemsetAsync(ctx->counters64.p, 0, 128, ctx->stream)); if (ctx->wtotals.p) HIPC(hipMemsetAsync(ctx->wtotals.p, 0, TOTALS_BYTES, ctx->stream)); HIPC(hipStreamSynchronize(ctx->stream));

@@ -123,20 +123,17 @@ static int32_t dev_Destroy(dev_ctx* ctx)
     (void)hipSetDevice(ctx->device);
     ctx->pending.clear();
     (void)hipStreamSynchronize(ctx->stream);
-    DevBuf* all[] = {&ctx->srgbLut, &ctx->texStage, &ctx->pmList, &ctx->pairNodes, &ctx->instRec, &ctx->entRec, &ctx->braidBuf, &ctx->unodes, &ctx->utlas, &ctx->uTabs, &ctx->uniBuf, &ctx->uniEntRec, &ctx->itlas, &ctx->imarks, &ctx->ichunks, &ctx->wnodes, &ctx->wleaf, &ctx->wids, &ctx->wpair, &ctx->wcounts, &ctx->wtotals, &ctx->nodes, &ctx->tris, &ctx->triVerts, &ctx->descs, &ctx->instances, &ctx->tlas, &ctx->parents, &ctx->leaves, &ctx->positions, &ctx->prevPositions, &ctx->vertices, &ctx->meshes,
+    DevBuf* all[] = {&ctx->srgbLut, &ctx->texStage, &ctx->pmList, &ctx->wtotals, &ctx->nodes, &ctx->tris, &ctx->triVerts, &ctx->descs, &ctx->instances, &ctx->tlas, &ctx->parents, &ctx->leaves, &ctx->positions, &ctx->prevPositions, &ctx->vertices, &ctx->meshes,
                      &ctx->materials, &ctx->xforms, &ctx->lights, &ctx->sky, &ctx->texDescs, &ctx->unskinned, &ctx->joints, &ctx->levelNodes, &ctx->tlasScratch, &ctx->queryIn, &ctx->queryOut, &ctx->queryRec, &ctx->queryList, &ctx->geomRays, &ctx->geomHits, &ctx->bandTab, &ctx->tileClass, &ctx->gbases, &ctx->camTab, &ctx->verTab, &ctx->trRec, &ctx->contFlag, &ctx->blockSums, &ctx->rayO, &ctx->rayT, &ctx->rayR, &ctx->aovA, &ctx->aovN, &ctx->hit,
                      &ctx->hitCost, &ctx->primHit, &ctx->queue[0], &ctx->queue[1], &ctx->keys[0], &ctx->keys[1], &ctx->keysTmp, &ctx->sortKeys, &ctx->sortVals, &ctx->contMask, &ctx->waveCounts,
                      &ctx->counts, &ctx->work, &ctx->qwork, &ctx->radSave, &ctx->deferCount, &ctx->sortHist, &ctx->counters64, &ctx->bases, &ctx->img[0], &ctx->img[1], &ctx->img[2]};
     for (DevBuf* b : all) b->release();
     for (auto& t : ctx->texData) t.release();
-    ctx->products.release_all();
+    ctx->products.release_all(); ctx->derived.release();
     ctx->denoiseStage.release(); ctx->skyStage.release();
     builder_scratch_free(ctx);
     if (ctx->hCounts) (void)hipHostFree(ctx->hCounts);
     if (ctx->hOverflow) (void)hipHostFree(ctx->hOverflow);
-    if (ctx->hInstOverlap) (void)hipHostFree(ctx->hInstOverlap);
-    if (ctx->hUni) (void)hipHostFree(ctx->hUni);
-    if (ctx->hPkStats) (void)hipHostFree(ctx->hPkStats);
     if (ctx->hBases) (void)hipHostFree(ctx->hBases);
     ctx->camStage.release(); ctx->verStage.release();
     if (ctx->hStage) (void)hipHostFree(ctx->hStage);
@@ -839,7 +836,7 @@ static int32_t dev_UpdateBuffer(dev_ctx* ctx, int32_t which, size_t offsetBytes,
             REQUIRE(why == nullptr, std::string("idkptUpdateBuffer: ") + (why ? why : ""));
             REQUIRE(ctx->st.BlasStackSize == 0 || ctx->st.BlasStackSize >= maxStack, "idkptUpdateBuffer: the patched BLAS needs a deeper traversal stack than the BlasStackSize set with idkptSetSettings");
             HIPC(hipMemcpyAsync(cur + offsetBytes, data, bytes, hipMemcpyHostToDevice, ctx->stream));
-            ctx->sceneStack = maxStack; ctx->pairValid = false; ctx->wideTopoValid = false; ctx->wideFillValid = false; ctx->itlasValid = false; ctx->instRecValid = false; ctx->imarksValid = false;   // (the tree itself may have changed: the wide nodes, the library's own TLAS and the triangle marks are derived anew)
+            ctx->sceneStack = maxStack; ctx->derived.invalidate(derived::Cause::NodesPatched);   // (the tree itself may have changed: the wide nodes, the library's own TLAS and the triangle marks are derived anew)
             ctx->sceneNested = blas_nested((const GpuBlasNode*)h.data(), ctx->hDescs.data(), (int)ctx->hDescs.size());
         } else {
             const char* why = nullptr;
@@ -856,7 +853,7 @@ static int32_t dev_UpdateBuffer(dev_ctx* ctx, int32_t which, size_t offsetBytes,
     char* dst = (char*)b->p;
     if (vb >= 0) { char* src; int rc = ver_writable(ctx, vb, offsetBytes == 0 && bytes == cap, &src, &dst); if (rc) return rc; }
     { int rc = staged_upload(ctx, dst + offsetBytes, data, bytes); if (rc) return rc; }   // (small updates — joints, transforms — do not wait for the stream)
-    if (which == IDKPT_BUF_MESH_TRANSFORMS && offsetBytes + bytes <= ctx->hXforms.size()) memcpy(ctx->hXforms.data() + offsetBytes, data, bytes);   // (the host's copy: "do all instances share one InvModel", host_launch.hpp)
+    if (which == IDKPT_BUF_MESH_TRANSFORMS && offsetBytes + bytes <= ctx->hXforms.size()) memcpy(ctx->hXforms.data() + offsetBytes, data, bytes);   // (the host's copy: "do all instances share one InvModel", host_derived.hpp)
     if (which == IDKPT_BUF_VERTEX_POSITIONS) { int rc = regather_triverts(ctx, 0, (uint32_t)ctx->triCount); if (rc) return rc; }
     return IDKPT_OK;
 }
@@ -869,7 +866,7 @@ static int32_t dev_DownloadBuffer(dev_ctx* ctx, int32_t which, size_t offsetByte
         HIPC(hipSetDevice(ctx->device));
         FLUSH();
         { int rc = wide_prepare(ctx); if (rc) return rc; }
-        DevBuf& wbuf = which == IDKPT_BUF_WIDE_NODES ? ctx->wnodes : (which == IDKPT_BUF_WIDE_LEAVES ? ctx->wleaf : ctx->wcounts);
+        DevBuf& wbuf = which == IDKPT_BUF_WIDE_NODES ? ctx->derived.wnodes : (which == IDKPT_BUF_WIDE_LEAVES ? ctx->derived.wleaf : ctx->derived.wcounts);
         REQUIRE(offsetBytes + bytes <= (which == IDKPT_BUF_WIDE_COUNTS ? ctx->hDescs.size() * 8 : wbuf.bytes), "idkptDownloadBuffer: bad buffer/range");
         HIPC(hipMemcpyAsync(dst, (char*)wbuf.p + offsetBytes, bytes, hipMemcpyDeviceToHost, ctx->stream));
         HIPC(hipStreamSynchronize(ctx->stream));

@@ -49,8 +49,9 @@ using namespace ptd;
 #include "host_kernel.hpp"
 #include "host_context.hpp"
 #include "walk_plan.hpp"
-#include "host_launch.hpp"
 #include "host_frame.hpp"
+#include "host_derived.hpp"
+#include "host_launch.hpp"
 #include "host_scene.hpp"
 #include "host_builder.hpp"
 #include "host_queries.hpp"
