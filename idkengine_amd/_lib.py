@@ -25,6 +25,7 @@ SYMBOLS = [
     "idkptCaptureGeometry", "idkptDownloadGeometry", "idkptGetGeometryDevicePtr", "idkptReproject", "idkptDownloadTemporal", "idkptGetTemporalDevicePtr", "idkptUseTemporalAsDenoised",
     "idkptSetDenoiseInput", "idkptGetDenoiseInput",
     "idkptReprojectMoments", "idkptDownloadTemporalMoments", "idkptGetTemporalMomentsDevicePtr", "idkptDenoiseTemporal",
+    "idkptCaptureMotion", "idkptDownloadMotion", "idkptGetMotionDevicePtr",
 ]
 
 _lib = None
@@ -64,6 +65,7 @@ def load():
         "idkptSetDenoiseInput": [vp, i32], "idkptGetDenoiseInput": [vp, C.POINTER(i32)],
         "idkptReprojectMoments": [vp, i32, i32, vp], "idkptDownloadTemporalMoments": [vp, i32, vp, sz], "idkptGetTemporalMomentsDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(sz)],
         "idkptDenoiseTemporal": [vp, i32, vp],
+        "idkptCaptureMotion": [vp, i32], "idkptDownloadMotion": [vp, i32, vp, sz], "idkptGetMotionDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(sz)],
         "idkptRefitBlas": [vp, i32], "idkptUploadUnskinnedVertices": [vp, vp, i32], "idkptSkin": [vp, u32, u32, u32, u32],
         "idkptDownloadBuffer": [vp, i32, sz, sz, vp], "idkptResetAccumulation": [vp], "idkptSetSampleSequence": [vp, u32, u32], "idkptGetAccumulatedSamples": [vp, C.POINTER(u32)],
         "idkptRender": [vp], "idkptSynchronize": [vp], "idkptDownload": [vp, i32, vp, sz], "idkptDownloadRays": [vp, vp, sz],

@@ -112,11 +112,13 @@ struct NoiseSlot {
 };
 
 // idkptCaptureGeometry / idkptReproject / idkptReprojectMoments: the geometry image (world position or miss direction, id bits), the temporal image (rgb, effective sample
-// count) and the temporal moments image (M1, M2, 0, effective sample count), all RGBA32F
+// count) and the temporal moments image (M1, M2, 0, effective sample count); idkptCaptureMotion: the motion image (the previous world position of the hit surface, id
+// bits; a miss: the geometry record).  All RGBA32F
 struct TemporalSlot {
-    GuardedBuf geom, temporal, moments;
+    GuardedBuf geom, temporal, moments, motion;
     bool geomValid = false, temporalValid = false, momentsValid = false;     // captured / reprojected / moments reprojected since the last resize
-    void release() { geom.release(); temporal.release(); moments.release(); geomValid = false; temporalValid = false; momentsValid = false; }
+    bool motionValid = false;                                                // the geometry image came from idkptCaptureMotion and `motion` belongs to it (idkptCaptureGeometry drops it)
+    void release() { geom.release(); temporal.release(); moments.release(); motion.release(); geomValid = false; temporalValid = false; momentsValid = false; motionValid = false; }
 };
 
 static bool slot_holds(const DisplaySlot& s) { return s.format >= 0; }
@@ -312,6 +314,11 @@ struct dev_ctx {
     PinnedUpload denoiseStage;      // idkptUploadDenoised's host image
     int denoiseInput = 0;           // idkptSetDenoiseInput (enum idkpt_denoise_input): where idkptDenoise takes its colour from; a state of its own, kept by every resize
     DevBuf geomRays, geomHits;      // idkptCaptureGeometry: the centre rays of one frame and their hits (W * rows of each), kept between calls
+    // idkptCaptureMotion: the local positions the vertices had BEFORE the last idkptSkin that wrote them (12 B per vertex; the reference's prevVertexPositionSSBO, which starts as
+    // a copy of the positions: ModelManager.cs:620).  Made at the context's first idkptCaptureMotion as a copy of the positions and kept from then on (motionPrevOn):
+    // idkptUploadScene re-creates it, idkptSkin copies the range it is about to replace.  Every write and every read is a copy or a kernel on the context's stream, issued
+    // when the call is made — never a queued sample — so one array serves any number of scene versions (positions themselves are not versioned either: ver_writable).
+    DevBuf motionPrev; bool motionPrevOn = false;
     int noiseOn = 0;                // idkptSetNoiseEstimate: FinalDraw folds every sample's luminance into the moments images as well; a state of its own, kept by every resize
     DevBuf camTab;                                       // per-sample cameras of the batch being launched (ring mode)
     int rowLimit = 0x7fffffff;                           // idkptSetRowRange: at most this many local rows

@@ -3,49 +3,64 @@
 // image and the temporal moments image of a ring slot (kernels: kernels_reproject.hpp; the contract: include/idkpt.h, "temporal reprojection" and "temporal moments").  Part of the single translation unit idkpt.hip (included there, behind host_queries.hpp, whose closest-hit core traces the centre rays, and
 // host_denoise.hpp, whose scope check and slot record it uses).
 // Queued samples are launched first, nothing but the downloads waits for the GPU.  Frame products (host_context.hpp, "frame products": the life cycle of the buffers): a
-// TemporalSlot per ring slot, all three images RGBA32F of the render size; the ray and hit scratch of a capture belongs to the context and is sized for one frame.
+// TemporalSlot per ring slot, all images RGBA32F of the render size; the ray and hit scratch of a capture belongs to the context and is sized for one frame.
+// idkptCaptureMotion / idkptDownloadMotion / idkptGetMotionDevicePtr ("motion-aware capture"): the slot's fourth image, the previous world position of what each pixel
+// sees; a slot that holds one is reprojected through it.  The previous vertex positions it reads (dev_ctx::motionPrev) are kept by host_scene.hpp.
 // One device, the whole frame (the scope of idkptDenoise): a pixel's history may lie in any row.
 #pragma once
 
-static int32_t dev_CaptureGeometry(dev_ctx* ctx, int32_t slot)
+// idkptCaptureGeometry (motion = false) and idkptCaptureMotion (motion = true): the centre rays of the current camera, their closest hits, and the records made of them —
+// the geometry image alone (which drops the slot's motion image), or the geometry image and the motion image in one pass over the hits
+static int32_t capture_records(dev_ctx* ctx, const std::string& who, int32_t slot, bool motion)
 {
     if (!ctx) return IDKPT_ERR_INVALID_ARGUMENT;
-    REQUIRE(slot >= -1 && slot < ctx->ringSize, "idkptCaptureGeometry: slot outside the frame ring (-1: the current slot)");
-    { int rc = denoise_scope(ctx, "idkptCaptureGeometry"); if (rc) return rc; }
-    if (!ctx->haveScene) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptCaptureGeometry: no scene uploaded");
+    REQUIRE(slot >= -1 && slot < ctx->ringSize, who + ": slot outside the frame ring (-1: the current slot)");
+    { int rc = denoise_scope(ctx, who.c_str()); if (rc) return rc; }
+    if (!ctx->haveScene) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, who + ": no scene uploaded");
     if (slot < 0) slot = ctx->curSlot;
     HIPC(hipSetDevice(ctx->device));
     FLUSH_KEEP();                                        // stream-ordered behind what was queued (as idkptDenoise); the accumulation is not touched
     const int W = ctx->W, H = ctx->H;
     const size_t N = (size_t)W * ctx->rows;
-    REQUIRE(N < (1ull << 31), "idkptCaptureGeometry: too many pixels for one ray query");
+    REQUIRE(N < (1ull << 31), who + ": too many pixels for one ray query");
+    // Scene versions: the records are made of the CURRENT state (make_dscene's and vb_cur's slots), by kernels launched now.  A later update either finds the current slot
+    // unpinned and writes it in place, behind these kernels on the stream, or moves on to another slot (ver_writable); motionPrev has one state and only stream-ordered writers.
+    if (motion && !ctx->motionPrevOn) { int rc = motion_prev_reset(ctx); if (rc) return rc; }
     HIPC(ctx->geomRays.ensure(N * sizeof(idkpt_ray))); HIPC(ctx->geomHits.ensure(N * sizeof(idkpt_hit)));
     TemporalSlot& s = FrameProducts::slot(ctx->products.temporal, ctx->ringSize, slot);
     HIPC(s.geom.ensure(ctx->stream, N * 16));
+    if (motion) HIPC(s.motion.ensure(ctx->stream, N * 16));
     reprojk::Camera cam;
     memcpy(cam.invProj, ctx->invProj, sizeof(cam.invProj)); memcpy(cam.invView, ctx->invView, sizeof(cam.invView));   // the camera current at the call
     const dim3 grid((unsigned)((N + 255) / 256));
     hipLaunchKernelGGL(k_geom_rays, grid, dim3(256), 0, ctx->stream, cam, W, H, (uint32_t)N, ctx->geomRays.as<idkpt_ray>());
     HIPC(hipGetLastError());
     { int rc = dev_TraceRaysDevice(ctx, ctx->geomRays.as<idkpt_ray>(), N, 0u, ctx->geomHits.as<idkpt_hit>()); if (rc) return rc; }   // closest hit, no lights: the core idkptTraceRaysDevice is held to the oracle with
-    s.geomValid = false;                                 // (a refused trace launched nothing: the previous record stays)
-    hipLaunchKernelGGL(k_geom_pack, grid, dim3(256), 0, ctx->stream, (const idkpt_ray*)ctx->geomRays.as<idkpt_ray>(), (const idkpt_hit*)ctx->geomHits.as<idkpt_hit>(), (uint32_t)N, s.geom.as<float4>());
+    s.geomValid = false; s.motionValid = false;          // (a refused trace launched nothing: the previous records stay)
+    if (motion)
+        hipLaunchKernelGGL(k_geom_motion_pack, grid, dim3(256), 0, ctx->stream, (const idkpt_ray*)ctx->geomRays.as<idkpt_ray>(), (const idkpt_hit*)ctx->geomHits.as<idkpt_hit>(), (uint32_t)N,
+                           (const uint4*)ctx->tris.as<uint4>(), (uint32_t)ctx->triCount, (const float*)ctx->motionPrev.as<float>(), (uint32_t)ctx->vertexCount,
+                           (const float4*)vb_cur<float4>(ctx, VB_XFORMS), (uint32_t)ctx->xformCount, s.geom.as<float4>(), s.motion.as<float4>());
+    else
+        hipLaunchKernelGGL(k_geom_pack, grid, dim3(256), 0, ctx->stream, (const idkpt_ray*)ctx->geomRays.as<idkpt_ray>(), (const idkpt_hit*)ctx->geomHits.as<idkpt_hit>(), (uint32_t)N, s.geom.as<float4>());
     HIPC(hipGetLastError());
-    s.geomValid = true;
+    s.geomValid = true; s.motionValid = motion;
     return IDKPT_OK;
 }
+static int32_t dev_CaptureGeometry(dev_ctx* ctx, int32_t slot) { return capture_records(ctx, "idkptCaptureGeometry", slot, false); }
+static int32_t dev_CaptureMotion(dev_ctx* ctx, int32_t slot) { return capture_records(ctx, "idkptCaptureMotion", slot, true); }
 
-// the record of ring slot `slot` (-1: the current one) for the calls that read one of its three images
-enum TemporalImage { TEMPORAL_IMAGE = 0, GEOMETRY_IMAGE = 1, TEMPORAL_MOMENTS_IMAGE = 2 };
-static bool temporal_holds(const TemporalSlot& s, TemporalImage which) { return which == GEOMETRY_IMAGE ? s.geomValid : which == TEMPORAL_IMAGE ? s.temporalValid : s.momentsValid; }
-static const GuardedBuf& temporal_buf(const TemporalSlot& s, TemporalImage which) { return which == GEOMETRY_IMAGE ? s.geom : which == TEMPORAL_IMAGE ? s.temporal : s.moments; }
+// the record of ring slot `slot` (-1: the current one) for the calls that read one of its four images
+enum TemporalImage { TEMPORAL_IMAGE = 0, GEOMETRY_IMAGE = 1, TEMPORAL_MOMENTS_IMAGE = 2, MOTION_IMAGE = 3 };
+static bool temporal_holds(const TemporalSlot& s, TemporalImage which) { return which == GEOMETRY_IMAGE ? s.geomValid : which == TEMPORAL_IMAGE ? s.temporalValid : which == MOTION_IMAGE ? s.motionValid : s.momentsValid; }
+static const GuardedBuf& temporal_buf(const TemporalSlot& s, TemporalImage which) { return which == GEOMETRY_IMAGE ? s.geom : which == TEMPORAL_IMAGE ? s.temporal : which == MOTION_IMAGE ? s.motion : s.moments; }
 static int32_t temporal_slot_of(dev_ctx* ctx, const char* who, int32_t slot, TemporalImage which, TemporalSlot** out)
 {
     REQUIRE(slot >= -1 && slot < ctx->ringSize, std::string(who) + ": slot outside the frame ring (-1: the current slot)");
     if (slot < 0) slot = ctx->curSlot;
     std::vector<TemporalSlot>& v = ctx->products.temporal;
     if ((size_t)slot >= v.size() || !temporal_holds(v[slot], which))
-        return fail(ctx, IDKPT_ERR_INVALID_OPERATION, std::string(who) + (which == GEOMETRY_IMAGE ? ": the slot holds no geometry image since the last resize (idkptCaptureGeometry)" : which == TEMPORAL_IMAGE ? ": the slot holds no temporal image since the last resize (idkptReproject)" : ": the slot holds no temporal moments image since the last resize (idkptReprojectMoments)"));
+        return fail(ctx, IDKPT_ERR_INVALID_OPERATION, std::string(who) + (which == GEOMETRY_IMAGE ? ": the slot holds no geometry image since the last resize (idkptCaptureGeometry)" : which == TEMPORAL_IMAGE ? ": the slot holds no temporal image since the last resize (idkptReproject)" : which == MOTION_IMAGE ? ": the slot holds no motion image (idkptCaptureMotion; idkptCaptureGeometry and every resize drop it)" : ": the slot holds no temporal moments image since the last resize (idkptReprojectMoments)"));
     *out = &v[slot];
     return IDKPT_OK;
 }
@@ -74,6 +89,8 @@ static int32_t dev_DownloadTemporal(dev_ctx* ctx, int32_t slot, float* rgba, siz
 static int32_t dev_GetTemporalDevicePtr(dev_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes) { return temporal_device_ptr(ctx, "idkptGetTemporalDevicePtr", slot, TEMPORAL_IMAGE, outPtr, outBytes); }
 static int32_t dev_DownloadTemporalMoments(dev_ctx* ctx, int32_t slot, float* rgba, size_t bytes) { return temporal_download(ctx, "idkptDownloadTemporalMoments", slot, TEMPORAL_MOMENTS_IMAGE, rgba, bytes); }
 static int32_t dev_GetTemporalMomentsDevicePtr(dev_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes) { return temporal_device_ptr(ctx, "idkptGetTemporalMomentsDevicePtr", slot, TEMPORAL_MOMENTS_IMAGE, outPtr, outBytes); }
+static int32_t dev_DownloadMotion(dev_ctx* ctx, int32_t slot, float* rgba, size_t bytes) { return temporal_download(ctx, "idkptDownloadMotion", slot, MOTION_IMAGE, rgba, bytes); }
+static int32_t dev_GetMotionDevicePtr(dev_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes) { return temporal_device_ptr(ctx, "idkptGetMotionDevicePtr", slot, MOTION_IMAGE, outPtr, outBytes); }
 
 static int32_t dev_Reproject(dev_ctx* ctx, int32_t slot, int32_t historySlot, const idkpt_reproject* r)
 {
@@ -107,7 +124,10 @@ static int32_t dev_Reproject(dev_ctx* ctx, int32_t slot, int32_t historySlot, co
     const dim3 grid((unsigned)((W + reprojk::TILE - 1) / reprojk::TILE), (unsigned)((H + reprojk::TILE - 1) / reprojk::TILE));
     const float4* hg = start ? nullptr : v[historySlot].geom.as<const float4>();
     const float4* hc = start ? nullptr : v[historySlot].temporal.as<const float4>();
-    hipLaunchKernelGGL(k_reproject, grid, dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, IDKPT_IMAGE_RESULT, slot), s.geom.as<const float4>(), hg, hc, s.temporal.as<float4>(), p);
+    if (!start && s.motionValid)                         // the slot's surfaces are looked up where they stood in the history frame (idkptCaptureMotion)
+        hipLaunchKernelGGL(k_reproject_motion<false>, grid, dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, IDKPT_IMAGE_RESULT, slot), s.geom.as<const float4>(), s.motion.as<const float4>(), hg, hc, s.temporal.as<float4>(), p);
+    else
+        hipLaunchKernelGGL(k_reproject, grid, dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, IDKPT_IMAGE_RESULT, slot), s.geom.as<const float4>(), hg, hc, s.temporal.as<float4>(), p);
     HIPC(hipGetLastError());
     s.temporalValid = true;
     return IDKPT_OK;
@@ -149,7 +169,10 @@ static int32_t dev_ReprojectMoments(dev_ctx* ctx, int32_t slot, int32_t historyS
     const dim3 grid((unsigned)((W + reprojk::TILE - 1) / reprojk::TILE), (unsigned)((H + reprojk::TILE - 1) / reprojk::TILE));
     const float4* hg = start ? nullptr : v[historySlot].geom.as<const float4>();
     const float4* hm = start ? nullptr : v[historySlot].moments.as<const float4>();
-    hipLaunchKernelGGL(k_reproject_moments, grid, dim3(256), 0, ctx->stream, (const float4*)noise_moments_ptr(ctx, slot), s.geom.as<const float4>(), hg, hm, s.moments.as<float4>(), p);
+    if (!start && s.motionValid)                         // (as idkptReproject: the same lookup record, so the count stays the temporal alpha)
+        hipLaunchKernelGGL(k_reproject_motion<true>, grid, dim3(256), 0, ctx->stream, (const float4*)noise_moments_ptr(ctx, slot), s.geom.as<const float4>(), s.motion.as<const float4>(), hg, hm, s.moments.as<float4>(), p);
+    else
+        hipLaunchKernelGGL(k_reproject_moments, grid, dim3(256), 0, ctx->stream, (const float4*)noise_moments_ptr(ctx, slot), s.geom.as<const float4>(), hg, hm, s.moments.as<float4>(), p);
     HIPC(hipGetLastError());
     s.momentsValid = true;
     return IDKPT_OK;

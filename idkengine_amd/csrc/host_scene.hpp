@@ -124,7 +124,7 @@ static int32_t dev_Destroy(dev_ctx* ctx)
     ctx->pending.clear();
     (void)hipStreamSynchronize(ctx->stream);
     DevBuf* all[] = {&ctx->srgbLut, &ctx->texStage, &ctx->pmList, &ctx->wtotals, &ctx->nodes, &ctx->tris, &ctx->triVerts, &ctx->descs, &ctx->instances, &ctx->tlas, &ctx->parents, &ctx->leaves, &ctx->positions, &ctx->prevPositions, &ctx->vertices, &ctx->meshes,
-                     &ctx->materials, &ctx->xforms, &ctx->lights, &ctx->sky, &ctx->texDescs, &ctx->unskinned, &ctx->joints, &ctx->levelNodes, &ctx->tlasScratch, &ctx->queryIn, &ctx->queryOut, &ctx->queryRec, &ctx->queryList, &ctx->geomRays, &ctx->geomHits, &ctx->bandTab, &ctx->tileClass, &ctx->gbases, &ctx->camTab, &ctx->verTab, &ctx->trRec, &ctx->contFlag, &ctx->blockSums, &ctx->rayO, &ctx->rayT, &ctx->rayR, &ctx->aovA, &ctx->aovN, &ctx->hit,
+                     &ctx->materials, &ctx->xforms, &ctx->lights, &ctx->sky, &ctx->texDescs, &ctx->unskinned, &ctx->joints, &ctx->levelNodes, &ctx->tlasScratch, &ctx->queryIn, &ctx->queryOut, &ctx->queryRec, &ctx->queryList, &ctx->geomRays, &ctx->geomHits, &ctx->motionPrev, &ctx->bandTab, &ctx->tileClass, &ctx->gbases, &ctx->camTab, &ctx->verTab, &ctx->trRec, &ctx->contFlag, &ctx->blockSums, &ctx->rayO, &ctx->rayT, &ctx->rayR, &ctx->aovA, &ctx->aovN, &ctx->hit,
                      &ctx->hitCost, &ctx->primHit, &ctx->queue[0], &ctx->queue[1], &ctx->keys[0], &ctx->keys[1], &ctx->keysTmp, &ctx->sortKeys, &ctx->sortVals, &ctx->contMask, &ctx->waveCounts,
                      &ctx->counts, &ctx->work, &ctx->qwork, &ctx->radSave, &ctx->deferCount, &ctx->sortHist, &ctx->counters64, &ctx->bases, &ctx->img[0], &ctx->img[1], &ctx->img[2]};
     for (DevBuf* b : all) b->release();
@@ -277,6 +277,15 @@ static int upload(dev_ctx* ctx, DevBuf& b, const void* src, size_t bytes)
 {
     HIPC(b.ensure(std::max<size_t>(bytes, 16)));
     if (bytes) HIPC(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    return IDKPT_OK;
+}
+// dev_ctx::motionPrev becomes a stream-ordered copy of the resident positions: the context's first idkptCaptureMotion, and every idkptUploadScene after it
+static int motion_prev_reset(dev_ctx* ctx)
+{
+    const size_t bytes = (size_t)ctx->vertexCount * 12;
+    HIPC(ctx->motionPrev.ensure(std::max<size_t>(bytes, 16)));
+    if (bytes) HIPC(hipMemcpyAsync(ctx->motionPrev.p, ctx->positions.p, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->motionPrevOn = true;
     return IDKPT_OK;
 }
 
@@ -460,6 +469,7 @@ static int32_t dev_UploadScene(dev_ctx* ctx, const idkpt_scene_desc* sc)
     ctx->nodeCount = sc->BlasNodeCount; ctx->triCount = sc->BlasTriangleCount; ctx->instanceCount = sc->BlasInstanceCount; ctx->tlasCount = sc->TlasNodes ? sc->TlasNodeCount : 0;
     ctx->vertexCount = sc->VertexCount; ctx->meshCount = sc->MeshCount; ctx->materialCount = sc->MaterialCount; ctx->xformCount = sc->MeshTransformCount;
     ctx->lightCount = sc->Lights ? sc->LightCount : 0; ctx->textureCount = sc->TextureCount;
+    if (ctx->motionPrevOn && (rc = motion_prev_reset(ctx))) return rc;   // (the previous positions of a new scene are its positions)
     ctx->hDescs.assign(sc->BlasDescs, sc->BlasDescs + sc->BlasDescCount); ctx->hInst0Blas = (int)sc->BlasInstances[0].BlasId;
     ctx->hInstances.assign(sc->BlasInstances, sc->BlasInstances + sc->BlasInstanceCount);
     ctx->hXforms.assign((const char*)sc->MeshTransforms, (const char*)sc->MeshTransforms + (size_t)sc->MeshTransformCount * sizeof(GpuMeshTransform));
@@ -880,6 +890,14 @@ static int32_t dev_DownloadBuffer(dev_ctx* ctx, int32_t which, size_t offsetByte
         HIPC(hipStreamSynchronize(ctx->stream));
         return IDKPT_OK;
     }
+    if (which == IDKPT_BUF_MOTION_PREV_POSITIONS) {   // idkptCaptureMotion's previous positions (copies and kernels in stream order only: nothing queued reads or writes them)
+        if (!ctx->haveScene || !ctx->motionPrevOn) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptDownloadBuffer: no motion previous positions before the first idkptCaptureMotion");
+        REQUIRE(offsetBytes + bytes <= (size_t)ctx->vertexCount * 12, "idkptDownloadBuffer: bad buffer/range");
+        HIPC(hipSetDevice(ctx->device));
+        HIPC(hipMemcpyAsync(dst, (char*)ctx->motionPrev.p + offsetBytes, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        HIPC(hipStreamSynchronize(ctx->stream));
+        return IDKPT_OK;
+    }
     size_t cap = 0; int vb = -1; DevBuf* b = which_buffer(ctx, which, &cap, &vb);
     REQUIRE(b != nullptr && offsetBytes + bytes <= cap, "idkptDownloadBuffer: bad buffer/range");
     HIPC(hipSetDevice(ctx->device));
@@ -1012,6 +1030,9 @@ static int32_t dev_Skin(dev_ctx* ctx, uint32_t inOff, uint32_t outOff, uint32_t 
     }
     // positions are read by update kernels only (stream order); the re-compressed normals / tangents go to a vertex slot no queued sample reads (ver_writable)
     char *vsrc, *vdst; { int rc = ver_writable(ctx, VB_VERTICES, outOff == 0 && count == (uint32_t)ctx->vertexCount, &vsrc, &vdst); if (rc) return rc; }
+    // idkptCaptureMotion's previous positions: the range as the skin is about to read it, in stream order in front of the kernel (idkptUpdateBuffer of positions does NOT
+    // write them, as in the reference: only Skinning writes prevVertexPositionSSBO)
+    if (count && ctx->motionPrevOn) HIPC(hipMemcpyAsync((char*)ctx->motionPrev.p + (size_t)outOff * 12, (const char*)ctx->positions.p + (size_t)outOff * 12, (size_t)count * 12, hipMemcpyDeviceToDevice, ctx->stream));
     if (count) hipLaunchKernelGGL(k_skin, dim3((count + 63) / 64), dim3(64), 0, ctx->stream, ctx->unskinned.as<GpuUnskinnedVertex>(), ctx->joints.as<float4>(), ctx->positions.as<float>(),
                                   ctx->prevPositions.as<float>(), (const uint4*)vsrc, (uint4*)vdst, inOff, outOff, jointOff, count);
     HIPC(hipGetLastError());

@@ -960,6 +960,10 @@ int32_t idkptReprojectMoments(idkpt_ctx* c, int32_t slot, int32_t historySlot, c
 int32_t idkptDownloadTemporalMoments(idkpt_ctx* c, int32_t slot, float* rgba, size_t bytes) { ONE_ONLY("idkptDownloadTemporalMoments", REPROJECT_WHY, dev_DownloadTemporalMoments(m, slot, rgba, bytes)); }
 int32_t idkptGetTemporalMomentsDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size_t* outBytes) { ONE_ONLY("idkptGetTemporalMomentsDevicePtr", REPROJECT_WHY, dev_GetTemporalMomentsDevicePtr(m, slot, outPtr, outBytes)); }
 int32_t idkptDenoiseTemporal(idkpt_ctx* c, int32_t slot, const idkpt_denoise_temporal* settings) { ONE_ONLY("idkptDenoiseTemporal", DENOISE_WHY, dev_DenoiseTemporal(m, slot, settings)); }
+// ---- motion-aware capture (host_reproject.hpp): the geometry image and the previous world position of what each pixel sees
+int32_t idkptCaptureMotion(idkpt_ctx* c, int32_t slot) { ONE_ONLY("idkptCaptureMotion", REPROJECT_WHY, dev_CaptureMotion(m, slot)); }
+int32_t idkptDownloadMotion(idkpt_ctx* c, int32_t slot, float* rgba, size_t bytes) { ONE_ONLY("idkptDownloadMotion", REPROJECT_WHY, dev_DownloadMotion(m, slot, rgba, bytes)); }
+int32_t idkptGetMotionDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size_t* outBytes) { ONE_ONLY("idkptGetMotionDevicePtr", REPROJECT_WHY, dev_GetMotionDevicePtr(m, slot, outPtr, outBytes)); }
 
 int32_t idkptResetAccumulation(idkpt_ctx* c) { if (!c) return IDKPT_ERR_INVALID_ARGUMENT; for (dev_ctx* m : c->dev) dev_ResetAccumulation(m); return IDKPT_OK; }
 int32_t idkptSetSampleSequence(idkpt_ctx* c, uint32_t first, uint32_t stride) { REPLICATE(SetSampleSequence, first, stride); }

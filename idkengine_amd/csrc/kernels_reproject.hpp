@@ -12,8 +12,11 @@
 //    not already serve), no scratch; the camera travels in the kernel arguments.
 //  * k_reproject_moments (idkptReprojectMoments): the same mapping and the same gathers on the slot's luminance moments and the history slot's temporal moments image.
 //  * k_temporal_to_denoised: rgb of the temporal image with alpha 1.0, the denoised image's format.
+//  * k_geom_motion_pack (idkptCaptureMotion): k_geom_pack fused with the motion record of motion_texel.hpp — where the hit surface stood in the previous frame;
+//    k_reproject_motion<MOMENTS>: the two reprojections of a slot that holds such a record.  Measured: profiles/motion.md.
 #pragma once
 #include "reproject_texel.hpp"
+#include "motion_texel.hpp"
 
 namespace reprojk {
 
@@ -56,6 +59,37 @@ __global__ __launch_bounds__(256) void k_geom_pack(const idkpt_ray* __restrict__
     out[i] = make_float4(r.x, r.y, r.z, r.w);
 }
 
+// idkptCaptureMotion: k_geom_pack's grid and mapping; the ray and the hit are read once (64 B) and BOTH records written (2 x 16 B), all coalesced.  A hit gathers its
+// triangle's indices (16 B), the three previous positions (3 x 12 B of motionPrev) and the PrevModel rows of its instance (48 B: float4 6-8 of the nine per transform, the
+// convention of load_inv_model_at): primary hits of neighbouring pixels share triangles and transforms, so the caches serve the gathers.  No LDS, no scratch, no atomics.
+// Every id is checked against its table before it feeds an address (motion_texel.hpp); geom is written exactly as k_geom_pack writes it.
+__global__ __launch_bounds__(256) void k_geom_motion_pack(const idkpt_ray* __restrict__ rays, const idkpt_hit* __restrict__ hits, uint32_t N, const uint4* __restrict__ tris, uint32_t triCount,
+                                                          const float* __restrict__ motionPrev, uint32_t vertexCount, const float4* __restrict__ xforms, uint32_t xformCount,
+                                                          float4* __restrict__ geom, float4* __restrict__ motion)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const float4 a = ((const float4*)rays)[2 * (size_t)i], b = ((const float4*)rays)[2 * (size_t)i + 1];
+    const float4 t = ((const float4*)hits)[2 * (size_t)i];                      // T, BaryX, BaryY, TriangleId
+    const uint2 h = ((const uint2*)hits)[4 * (size_t)i + 2];                  // MeshTransformId, Hit
+    const float o[3] = {a.x, a.y, a.z}, d[3] = {b.x, b.y, b.z};
+    const reprojt::V4 r = reprojt::pack_record(o, d, t.x, h.x, h.y != 0u);
+    reprojt::V4 m = r;                                                         // a miss: the same record
+    const uint32_t tri = __float_as_uint(t.w);
+    if (h.y != 0u && motiont::ids_resident(tri, triCount, h.x, xformCount)) {
+        const uint4 v = tris[tri];
+        if (motiont::vertices_resident(v.x, v.y, v.z, vertexCount)) {
+            const float* p0 = motionPrev + 3 * (size_t)v.x; const float* p1 = motionPrev + 3 * (size_t)v.y; const float* p2 = motionPrev + 3 * (size_t)v.z;
+            const float q0[3] = {p0[0], p0[1], p0[2]}, q1[3] = {p1[0], p1[1], p1[2]}, q2[3] = {p2[0], p2[1], p2[2]};
+            const float4* x = xforms + 9 * (size_t)h.x;
+            const float4 r0 = x[6], r1 = x[7], r2 = x[8];
+            m = motiont::prev_record(t.y, t.z, q0, q1, q2, reprojt::v4(r0.x, r0.y, r0.z, r0.w), reprojt::v4(r1.x, r1.y, r1.z, r1.w), reprojt::v4(r2.x, r2.y, r2.z, r2.w), h.x);
+        }
+    }
+    geom[i] = make_float4(r.x, r.y, r.z, r.w);
+    motion[i] = make_float4(m.x, m.y, m.z, m.w);
+}
+
 // grid (ceil(W / 16), ceil(H / 16)), 256 threads.  hg / hc: the history slot's images, or both null to start a history (out = (cur.rgb, n))
 __global__ __launch_bounds__(256) void k_reproject(const float4* __restrict__ cur, const float4* __restrict__ g, const float4* __restrict__ hg, const float4* __restrict__ hc,
                                                    float4* __restrict__ out, reprojt::Params p)
@@ -86,6 +120,25 @@ __global__ __launch_bounds__(256) void k_reproject_moments(const float4* __restr
     const float4 r = g[i];
     const MemFetch f = {hg, hm, p.W};
     const reprojt::V4 o = reprojt::reproject_moments_texel(f, p, m.x, m.y, reprojt::v4(r.x, r.y, r.z, r.w));
+    out[i] = make_float4(o.x, o.y, o.z, o.w);
+}
+
+// idkptReproject / idkptReprojectMoments of a slot that holds a MOTION image (idkptCaptureMotion) onto a history: k_reproject's / k_reproject_moments' grid, mapping and
+// gathers plus one more coalesced 16-byte read per pixel — the motion record mv[i], which is looked up in the history in place of the geometry record (the lookup record of
+// reproject_texel.hpp).  in: Result (MOMENTS: the moments image) of the slot; hg / hc: the history slot's geometry and temporal (MOMENTS: temporal moments) images, never null
+// (a history is started by the kernels above).  No LDS, no scratch.
+template <bool MOMENTS>
+__global__ __launch_bounds__(256) void k_reproject_motion(const float4* __restrict__ in, const float4* __restrict__ g, const float4* __restrict__ mv, const float4* __restrict__ hg,
+                                                          const float4* __restrict__ hc, float4* __restrict__ out, reprojt::Params p)
+{
+    using namespace reprojk;
+    const int x = (int)blockIdx.x * TILE + ((int)threadIdx.x & (TILE - 1)), y = (int)blockIdx.y * TILE + ((int)threadIdx.x >> 4);
+    if (x >= p.W || y >= p.H) return;
+    const size_t i = (size_t)y * (size_t)p.W + (size_t)x;
+    const float4 c = in[i], r = g[i], l = mv[i];
+    const MemFetch f = {hg, hc, p.W};
+    const reprojt::V4 rg = reprojt::v4(r.x, r.y, r.z, r.w), rl = reprojt::v4(l.x, l.y, l.z, l.w);
+    const reprojt::V4 o = MOMENTS ? reprojt::reproject_moments_texel(f, p, c.x, c.y, rg, rl) : reprojt::reproject_texel(f, p, reprojt::v4(c.x, c.y, c.z, c.w), rg, rl);
     out[i] = make_float4(o.x, o.y, o.z, o.w);
 }
 

@@ -52,18 +52,20 @@ REPROJECT_HD float dist2(float ax, float ay, float az, float bx, float by, float
     return (dx * dx + dy * dy) + dz * dz;
 }
 
-// One pixel.  cur = Result of the slot, g = its geometry record; fetch(qx, qy, &hg, &hc) returns the history slot's geometry record and temporal texel of an IN-IMAGE
-// position and is never called for one outside.  Returns (rgb, effective sample count).
+// One pixel.  cur = Result of the slot, g = its geometry record, l = its LOOKUP record: the point that is looked up in the history frame — g itself, or the slot's motion
+// record (motion_texel.hpp: where the surface stood when the history was captured; idkptCaptureMotion).  g supplies the id, l the position in the clip coordinates, in
+// the limit and in the tap test.  fetch(qx, qy, &hg, &hc) returns the history slot's geometry record and temporal texel of an IN-IMAGE position and is never called for
+// one outside.  Returns (rgb, effective sample count).
 template <class Fetch>
-REPROJECT_HD V4 reproject_texel(const Fetch& fetch, const Params& P, V4 cur, V4 g)
+REPROJECT_HD V4 reproject_texel(const Fetch& fetch, const Params& P, V4 cur, V4 g, V4 l)
 {
     const V4 none = v4(cur.x, cur.y, cur.z, P.n);
     const uint32_t id = bits_of(g.w);
     const bool miss = id == MISS_ID;
     const float* M = P.M;
-    float cx = (g.x * M[0] + g.y * M[4]) + g.z * M[8];
-    float cy = (g.x * M[1] + g.y * M[5]) + g.z * M[9];
-    float cw = (g.x * M[3] + g.y * M[7]) + g.z * M[11];
+    float cx = (l.x * M[0] + l.y * M[4]) + l.z * M[8];
+    float cy = (l.x * M[1] + l.y * M[5]) + l.z * M[9];
+    float cw = (l.x * M[3] + l.y * M[7]) + l.z * M[11];
     if (!miss) { cx = cx + M[12]; cy = cy + M[13]; cw = cw + M[15]; }          // a miss is a direction: w = 0
     if (!(cw > 0.0f)) return none;
     const float u = (cx / cw * 0.5f + 0.5f) * (float)P.W - 0.5f;
@@ -73,7 +75,7 @@ REPROJECT_HD V4 reproject_texel(const Fetch& fetch, const Params& P, V4 cur, V4 
     const float fx = u - x0f, fy = v - y0f;
     const int x0 = (int)x0f, y0 = (int)y0f;                                     // -1 .. W - 1, -1 .. H - 1
     const float wt[4] = {(1.0f - fx) * (1.0f - fy), fx * (1.0f - fy), (1.0f - fx) * fy, fx * fy};
-    const float limit = miss ? 0.0f : P.tol2 * dist2(g.x, g.y, g.z, P.prevPos[0], P.prevPos[1], P.prevPos[2]);
+    const float limit = miss ? 0.0f : P.tol2 * dist2(l.x, l.y, l.z, P.prevPos[0], P.prevPos[1], P.prevPos[2]);
     float sr = 0.0f, sg = 0.0f, sb = 0.0f, sa = 0.0f, sumW = 0.0f;
     for (int k = 0; k < 4; k++) {
         const int qx = x0 + (k & 1), qy = y0 + (k >> 1);
@@ -81,7 +83,7 @@ REPROJECT_HD V4 reproject_texel(const Fetch& fetch, const Params& P, V4 cur, V4 
         V4 hg, hc;
         fetch(qx, qy, &hg, &hc);
         if (bits_of(hg.w) != id) continue;
-        if (!miss && !(dist2(g.x, g.y, g.z, hg.x, hg.y, hg.z) <= limit)) continue;   // (false for a NaN on either side)
+        if (!miss && !(dist2(l.x, l.y, l.z, hg.x, hg.y, hg.z) <= limit)) continue;   // (false for a NaN on either side)
         if (!(finite(hc.x) && finite(hc.y) && finite(hc.z) && finite(hc.w))) continue;
         const float w = wt[k];
         sr = sr + hc.x * w; sg = sg + hc.y * w; sb = sb + hc.z * w; sa = sa + hc.w * w;
@@ -94,15 +96,21 @@ REPROJECT_HD V4 reproject_texel(const Fetch& fetch, const Params& P, V4 cur, V4 
     return v4((hr * Hc + cur.x * P.n) / den, (hgr * Hc + cur.y * P.n) / den, (hb * Hc + cur.z * P.n) / den, den);
 }
 
-// One pixel of idkptReprojectMoments: the same clip coordinates, taps, validity rules and blend on the luminance moments.  (m1, m2) of the slot's moments image, g its
-// geometry record; fetch returns the history slot's geometry record and TEMPORAL MOMENTS texel (M1, M2, 0, cnt).  Returns (M1, M2, 0, effective sample count): the third
-// channel is stored as 0 whatever the history held there.
+// ... without a motion record: the geometry record is looked up
 template <class Fetch>
-REPROJECT_HD V4 reproject_moments_texel(const Fetch& fetch, const Params& P, float m1, float m2, V4 g)
+REPROJECT_HD V4 reproject_texel(const Fetch& fetch, const Params& P, V4 cur, V4 g) { return reproject_texel(fetch, P, cur, g, g); }
+
+// One pixel of idkptReprojectMoments: the same clip coordinates, taps, validity rules and blend on the luminance moments.  (m1, m2) of the slot's moments image, g its
+// geometry record, l its lookup record; fetch returns the history slot's geometry record and TEMPORAL MOMENTS texel (M1, M2, 0, cnt).  Returns (M1, M2, 0, effective
+// sample count): the third channel is stored as 0 whatever the history held there.
+template <class Fetch>
+REPROJECT_HD V4 reproject_moments_texel(const Fetch& fetch, const Params& P, float m1, float m2, V4 g, V4 l)
 {
-    V4 o = reproject_texel(fetch, P, v4(m1, m2, 0.0f, 0.0f), g);
+    V4 o = reproject_texel(fetch, P, v4(m1, m2, 0.0f, 0.0f), g, l);
     o.z = 0.0f;
     return o;
 }
+template <class Fetch>
+REPROJECT_HD V4 reproject_moments_texel(const Fetch& fetch, const Params& P, float m1, float m2, V4 g) { return reproject_moments_texel(fetch, P, m1, m2, g, g); }
 
 }  // namespace reprojt

@@ -328,7 +328,8 @@ class Scene:
 
 # enum idkpt_buffer (include/idkpt.h)
 (IDKPT_BUF_MESH_TRANSFORMS, IDKPT_BUF_VERTEX_POSITIONS, IDKPT_BUF_VERTICES, IDKPT_BUF_MESHES, IDKPT_BUF_MATERIALS, IDKPT_BUF_LIGHTS,
- IDKPT_BUF_BLAS_NODES, IDKPT_BUF_TLAS_NODES, IDKPT_BUF_JOINT_MATRICES, IDKPT_BUF_WIDE_NODES, IDKPT_BUF_WIDE_LEAVES, IDKPT_BUF_WIDE_COUNTS, IDKPT_BUF_PREV_VERTEX_POSITIONS) = range(13)
+ IDKPT_BUF_BLAS_NODES, IDKPT_BUF_TLAS_NODES, IDKPT_BUF_JOINT_MATRICES, IDKPT_BUF_WIDE_NODES, IDKPT_BUF_WIDE_LEAVES, IDKPT_BUF_WIDE_COUNTS, IDKPT_BUF_PREV_VERTEX_POSITIONS,
+ IDKPT_BUF_MOTION_PREV_POSITIONS) = range(14)
 
 # GpuPerFrameData (include/idkpt_types.h; Source/GpuTypes/GpuPerFrameData.cs:5-21): the path tracer reads InvView, ViewPos and InvProjection
 GpuPerFrameData = np.dtype([("ProjView", "<f4", 16), ("View", "<f4", 16), ("InvView", "<f4", 16), ("PrevView", "<f4", 16), ("ViewPos", "<f4", 3), ("Frame", "<u4"),

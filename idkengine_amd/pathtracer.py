@@ -784,6 +784,29 @@ class PathTracer:
         self._check(self._L.idkptDenoiseTemporal(self._ctx, slot, C.addressof(settings)))
         return self.DownloadDenoised(slot)
 
+    # ---- motion-aware capture (idkptCaptureMotion): reprojection that follows moving objects; the reference's path tracer has no counterpart
+    def CaptureMotion(self, slot=None):
+        """idkptCaptureMotion: CaptureGeometry plus the slot's motion image — where each pixel's surface point stood in the previous frame (the previous vertex positions
+        through PrevModel).  Reproject / ReprojectMoments of a slot that holds one look the history up there.  CaptureGeometry on the slot drops it."""
+        self._check(self._L.idkptCaptureMotion(self._ctx, -1 if slot is None else int(slot)))
+
+    def DownloadMotion(self, slot=None):
+        """idkptDownloadMotion: (H, W, 4) float32 — the previous world position of the pixel centre's hit and the bits of its MeshTransformId, or the geometry record of a miss"""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.idkptDownloadMotion(self._ctx, -1 if slot is None else int(slot), out.ctypes.data, out.nbytes))
+        return out
+
+    def motion_device_ptr(self, slot=None):
+        """idkptGetMotionDevicePtr: (device pointer, bytes), valid in stream order; 64 guard bytes follow"""
+        p = C.c_void_p(); n = C.c_size_t()
+        self._check(self._L.idkptGetMotionDevicePtr(self._ctx, -1 if slot is None else int(slot), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def DownloadMotionPrevPositions(self, count):
+        """IDKPT_BUF_MOTION_PREV_POSITIONS: (count, 3) float32 — the local positions the first `count` vertices had before the last Skin that wrote them (the positions
+        themselves where none did); raises before the context's first CaptureMotion"""
+        return self.DownloadBuffer(T.IDKPT_BUF_MOTION_PREV_POSITIONS, np.float32, int(count) * 3).reshape(-1, 3)
+
     def enable_counters(self, on=True):
         self._check(self._L.idkptEnableCounters(self._ctx, 1 if on else 0))
 

@@ -356,20 +356,21 @@ def cornell_meshes(variant="diffuse"):
     return {"walls": [mk(walls, white), mk(left, red), mk(right, green), mk(lq, light)], "short": mk(short, short_m), "tall": mk(tall, tall_m)}
 
 
-def cornell_scene(builder, variant="diffuse", instanced=False, sky_color=(0.0, 0.0, 0.0)):
+def cornell_scene(builder, variant="diffuse", instanced=False, sky_color=(0.0, 0.0, 0.0), refittable=False):
     """instanced=False: all 32 triangles hoisted into one BLAS (boxes pre-transformed) — the layout the reference
     prefers (Application.cs:481).  instanced=True: walls / short box / tall box are three BLASes with their own
-    GpuMeshTransform, exercising RayTransform, the normal matrix and the TLAS."""
+    GpuMeshTransform, exercising RayTransform, the normal matrix and the TLAS.  refittable: every BLAS is built
+    with leaf / parent indices (animated boxes: idkptSkin + idkptRefitBlas)."""
     m = cornell_meshes(variant)
     xs = rotation_y(-18.0) @ translation((0.33, -1.0, 0.4)); xt = rotation_y(17.0) @ translation((-0.35, -1.0, -0.3))
     if instanced:
-        blases = [{"meshes": m["walls"]}, {"meshes": [m["short"]], "transform": xs}, {"meshes": [m["tall"]], "transform": xt}]
+        blases = [{"meshes": m["walls"], "refittable": refittable}, {"meshes": [m["short"]], "transform": xs, "refittable": refittable}, {"meshes": [m["tall"]], "transform": xt, "refittable": refittable}]
     else:
         def bake(mi, x):
             p = (np.c_[mi.positions.astype(np.float64), np.ones(len(mi.positions))] @ x)[:, :3].astype(np.float32)
             pp, ii, nn, tt = flat_shaded(p[mi.indices.reshape(-1)].reshape(-1, 3, 3))
             return MeshInput(pp, ii, mi.material, nn, tt)
-        blases = [{"meshes": m["walls"] + [bake(m["short"], xs), bake(m["tall"], xt)]}]
+        blases = [{"meshes": m["walls"] + [bake(m["short"], xs), bake(m["tall"], xt)], "refittable": refittable}]
     return assemble(blases, builder, sky_color=sky_color)
 
 

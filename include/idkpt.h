@@ -55,6 +55,9 @@ enum idkpt_buffer {
     /* idkptDownloadBuffer only (ABI 13) — what idkptSkin keeps of the positions it replaced (Skinning/compute.glsl:44, SSBO 9): packed float3 per vertex, VertexCount entries.
      * IDKPT_ERR_INVALID_OPERATION before the first idkptSkin; entries no idkptSkin has written yet read as zero. */
     IDKPT_BUF_PREV_VERTEX_POSITIONS = 12,
+    /* idkptDownloadBuffer only (added under ABI 13 with idkptCaptureMotion; detect by that symbol) — the previous positions idkptCaptureMotion reads ("motion-aware capture"
+     * below): packed float3 per vertex, VertexCount entries.  IDKPT_ERR_INVALID_OPERATION before the context's first idkptCaptureMotion. */
+    IDKPT_BUF_MOTION_PREV_POSITIONS = 13,
 };
 
 /* One image of the texture table + the sampler state it is sampled with (stand-in for the GL bindless samplers of GpuMaterial: a texture object and the GLSampler.SamplerState
@@ -247,7 +250,9 @@ typedef struct idkpt_stats {
  * 9 = idkptSetPresentationSize / idkptGetPresentationSize / idkptGetBloomRoute / idkptGetBloomChainDevicePtr, 10 = idkptDownloadTileClasses, 11 = idkptCollideSpheres / idkptCollideSpheresDevice,
  * 12 = idkptDenoise / idkptUploadDenoised / idkptDownloadDenoised / idkptGetDenoisedDevicePtr / idkptGetDenoiseRoute / idkptSetResultSource / idkptGetResultSource,
  * 13 = IDKPT_BUF_PREV_VERTEX_POSITIONS).  The noise-estimate entry points (idkptSetNoiseEstimate ... idkptGetMomentsDevicePtr, below) were added WITHOUT a new number: nothing a host of ABI 12 can
- * trip over changed, and a host that wants them looks the symbols up (dlsym / GetProcAddress: a library without them has none of the seven); idkptDenoiseVariance was added the same way.  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
+ * trip over changed, and a host that wants them looks the symbols up (dlsym / GetProcAddress: a library without them has none of the seven); idkptDenoiseVariance was added the same way,
+ * and so were the temporal calls and, last, idkptCaptureMotion / idkptDownloadMotion / idkptGetMotionDevicePtr with IDKPT_BUF_MOTION_PREV_POSITIONS (a library that exports idkptCaptureMotion knows the value;
+ * an older one answers it with IDKPT_ERR_INVALID_ARGUMENT, as every unknown buffer).  A host that does not compile against this header (the C# LibraryImport struct of INTEGRATION.md) passes the size
  * of ITS struct to idkptGetStatsSized and gets exactly that many bytes; idkptGetStats(ctx, out) is idkptGetStatsSized(ctx, out, sizeof(idkpt_stats)) of the header the LIBRARY
  * was built with — for hosts built from the same tree.  idkptGetAbiVersion() lets a host refuse a library older than the header it was written against. */
 #define IDKPT_ABI_VERSION 13
@@ -967,6 +972,49 @@ IDKPT_API int32_t idkptReprojectMoments(idkpt_ctx* ctx, int32_t slot, int32_t hi
 IDKPT_API int32_t idkptDownloadTemporalMoments(idkpt_ctx* ctx, int32_t slot, float* rgba, size_t bytes);
 IDKPT_API int32_t idkptGetTemporalMomentsDevicePtr(idkpt_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes);   /* stream-ordered; the guard bytes follow *outBytes */
 IDKPT_API int32_t idkptDenoiseTemporal(idkpt_ctx* ctx, int32_t slot, const idkpt_denoise_temporal* settings);        /* temporal image, temporal moments, Albedo and Normal of the slot -> its denoised image */
+
+/* ---- motion-aware capture (added under the same ABI number; detect by the symbol idkptCaptureMotion): reprojection that follows moving objects --------------------------
+ * THE PATH TRACER OF THE REFERENCE HAS NO COUNTERPART (it resets and waits); its rasterizer derives motion vectors from the same inputs (GBuffer/VertexPath/vertex.glsl:
+ * PrevProjView * prevModelMatrix * prevVertexPosition).  idkptReproject looks a pixel's CURRENT world position up in the history frame, so a surface that moved between
+ * the two captures fails the position test and starts over from one sample — on exactly the frames an animated host renders.  idkptCaptureMotion records, beside the
+ * geometry image, where each pixel's surface point stood in the previous frame; a slot that holds such a MOTION IMAGE is reprojected through it.  Everything is default-off
+ * and additive: no existing call, struct, enum value or image changes by a bit for a host that does not call idkptCaptureMotion.  Every operation of the texts below is a
+ * correctly rounded binary32 + - * in the written order (-ffp-contract=off); they are checked against an independent numpy restatement (tests/motion_ref.py) bit for bit.
+ *
+ * idkptCaptureMotion(ctx, slot) does what idkptCaptureGeometry does — the same centre rays of the current camera, the same closest-hit core, the same scope and refusals,
+ * and a geometry image equal to idkptCaptureGeometry's bit for bit — and fills the slot's motion image from the same hits: RGBA32F of the render size, allocated at its
+ * first use, followed by 64 guard bytes of 0xA5 that nothing writes, with the life cycle of the slot's other three images (kept by idkptResetAccumulation, idkptBeginFrame,
+ * idkptSetMaxBatch and idkptSetPresentationSize; released by idkptSetSize, idkptSetFrameRing with another count and every row-layout call).  Per pixel:
+ *   miss:  record = the geometry record (d.x, d.y, d.z, asfloat(0xFFFFFFFF)).
+ *   hit of triangle t (TriangleId) of transform m (MeshTransformId) at (BaryX, BaryY):
+ *     b  = (BaryX, BaryY, (1.0f - BaryX) - BaryY);  (vx, vy, vz) = the X, Y, Z vertex indices of triangle t: b.x weighs vx, b.y vy, b.z vz (the shading's convention)
+ *     q0, q1, q2 = the PREVIOUS local positions of vx, vy, vz (below);  l.c = (q0.c * b.x + q1.c * b.y) + q2.c * b.z for c = x, y, z
+ *     R_0 .. R_2 = the three rows of PrevModel of GpuMeshTransform m as resident at the call;  p'.r = ((R_r.x * l.x + R_r.y * l.y) + R_r.z * l.z) + R_r.w
+ *     record = (p'.x, p'.y, p'.z, asfloat(m))
+ *   A NaN or an infinity in a previous position or in PrevModel is carried into the record; idkptReproject's rules then give that pixel no history.
+ * idkptCaptureGeometry on a slot DROPS that slot's motion image (its geometry no longer belongs to it).  idkptDownloadMotion (bytes = height * width * 16) and
+ * idkptGetMotionDevicePtr read the image as idkptDownloadGeometry / idkptGetGeometryDevicePtr do; IDKPT_ERR_INVALID_OPERATION for a slot that holds none.
+ *
+ * The previous local positions.  IDKPT_BUF_PREV_VERTEX_POSITIONS (what idkptSkin keeps, zero where no idkptSkin wrote) is unchanged.  The capture reads a second array
+ * that follows the reference's prevVertexPositionSSBO, which starts as a copy of the positions (ModelManager.cs:620) and is overwritten by Skinning alone: it is made at
+ * the context's FIRST idkptCaptureMotion as a copy of the positions resident then (a context that never asks allocates nothing) and kept from then on; idkptUploadScene
+ * re-creates it from the new positions; idkptSkin copies the positions of its output range into it before it replaces them.  idkptUpdateBuffer of
+ * IDKPT_BUF_VERTEX_POSITIONS does NOT write it, as in the reference: vertices a host moves that way are treated as if they had always stood where they stand.  Readable
+ * as IDKPT_BUF_MOTION_PREV_POSITIONS through idkptDownloadBuffer.  A static vertex of an instance whose PrevModel equals its Model yields p' = the hit position up to the
+ * rounding of the two routes (barycentric interpolation against o + d * T): far inside the position tolerance.
+ * Scene versions (idkptSetSceneVersions): the capture launches what is queued and records the CURRENT state; all writes to the array are copies on the context's stream
+ * issued by the call that makes them, so one array serves any number of versions and results do not depend on the count.
+ *
+ * Reprojection.  idkptReproject and idkptReprojectMoments of a `slot` that holds a motion image, onto a history (not IDKPT_NO_HISTORY), use p' = the motion record's xyz
+ * in place of p = g.xyz in exactly three places of idkptReproject's text: the clip coordinates, the limit (PositionTolerance * PositionTolerance) * |p' - PrevViewPos|^2,
+ * and the tap test |p' - hg_q.xyz|^2 <= limit.  id (from g), the miss rule, the finiteness test, the weights, 0.01f, the cap and the blend are that text unchanged; a
+ * slot without a motion image runs what it ran before, bit for bit.  The history slot needs its geometry and temporal (moments) images only.  idkptReprojectMoments' count
+ * still equals the temporal alpha bit for bit.  The per-frame order of an animated host: update the transforms (Model, InvModel and PrevModel = the Model of the frame
+ * before), idkptSkin, idkptRefitBlas, the TLAS, render, idkptCaptureMotion, idkptReproject with the previous frame's camera.
+ * What is not followed: surfaces seen through a bounce, vertices moved by idkptUpdateBuffer, and disocclusions behind a mover keep the rules above (they start over). */
+IDKPT_API int32_t idkptCaptureMotion(idkpt_ctx* ctx, int32_t slot);                                          /* centre rays of the current camera -> the slot's geometry image and motion image */
+IDKPT_API int32_t idkptDownloadMotion(idkpt_ctx* ctx, int32_t slot, float* rgba, size_t bytes);
+IDKPT_API int32_t idkptGetMotionDevicePtr(idkpt_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes);      /* stream-ordered; the guard bytes follow *outBytes */
 
 /* ---- render ----------------------------------------------------------------------------- */
 /* PathTracer.ResetAccumulation (PathTracer.cs:334-337) */
