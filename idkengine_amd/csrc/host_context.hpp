@@ -113,12 +113,14 @@ struct NoiseSlot {
 
 // idkptCaptureGeometry / idkptReproject / idkptReprojectMoments: the geometry image (world position or miss direction, id bits), the temporal image (rgb, effective sample
 // count) and the temporal moments image (M1, M2, 0, effective sample count); idkptCaptureMotion: the motion image (the previous world position of the hit surface, id
-// bits; a miss: the geometry record).  All RGBA32F
+// bits; a miss: the geometry record); idkptReprojectFast: the fast temporal image (the temporal image's content under a short cap; idkptRectifyHistory, host_rectify.hpp,
+// pulls the temporal image towards it).  All RGBA32F
 struct TemporalSlot {
-    GuardedBuf geom, temporal, moments, motion;
+    GuardedBuf geom, temporal, moments, motion, fast;
     bool geomValid = false, temporalValid = false, momentsValid = false;     // captured / reprojected / moments reprojected since the last resize
     bool motionValid = false;                                                // the geometry image came from idkptCaptureMotion and `motion` belongs to it (idkptCaptureGeometry drops it)
-    void release() { geom.release(); temporal.release(); moments.release(); motion.release(); geomValid = false; temporalValid = false; momentsValid = false; motionValid = false; }
+    bool fastValid = false;                                                  // fast-reprojected since the last resize
+    void release() { geom.release(); temporal.release(); moments.release(); motion.release(); fast.release(); geomValid = false; temporalValid = false; momentsValid = false; motionValid = false; fastValid = false; }
 };
 
 static bool slot_holds(const DisplaySlot& s) { return s.format >= 0; }
@@ -127,10 +129,11 @@ template <class S> static bool slot_holds(const S& s) { return s.valid; }
 struct FrameProducts {
     std::vector<DisplaySlot> display; std::vector<BloomSlot> bloom; std::vector<DenoiseSlot> denoise; std::vector<NoiseSlot> noise; std::vector<TemporalSlot> temporal;
     DevBuf moments;              // idkptSetNoiseEstimate: the moments images (m1, m2, 0, 1) of ALL ring slots in one allocation, each followed by its guard (host_noise.hpp noise_moments_ensure)
+    GuardedBuf rectifySpare;     // idkptRectifyHistory: the image its kernel writes, swapped with the slot's temporal image behind the launch (one per context: the calls are stream-ordered); of the render size, released with the temporal images
     template <class S> static void drop(std::vector<S>& v) { for (S& s : v) s.release(); v.clear(); }
     void release_noise() { drop(noise); moments.release(); }
     void release_presentation_sized() { drop(display); drop(bloom); }
-    void release_all() { release_presentation_sized(); drop(denoise); release_noise(); drop(temporal); }
+    void release_all() { release_presentation_sized(); drop(denoise); release_noise(); drop(temporal); rectifySpare.release(); }
     // the record of a ring slot that is about to be made: the vector gets the ring's size at its first use after a release
     template <class S> static S& slot(std::vector<S>& v, int ringSize, int slot) { if (v.size() != (size_t)ringSize) { drop(v); v.resize(ringSize); } return v[slot]; }
 };

@@ -6,6 +6,8 @@
 // TemporalSlot per ring slot, all images RGBA32F of the render size; the ray and hit scratch of a capture belongs to the context and is sized for one frame.
 // idkptCaptureMotion / idkptDownloadMotion / idkptGetMotionDevicePtr ("motion-aware capture"): the slot's fourth image, the previous world position of what each pixel
 // sees; a slot that holds one is reprojected through it.  The previous vertex positions it reads (dev_ctx::motionPrev) are kept by host_scene.hpp.
+// idkptReprojectFast / idkptDownloadFastTemporal / idkptGetFastTemporalDevicePtr ("history rectification"): the slot's fifth image, a second temporal image with a short
+// cap, made by idkptReproject's body on another image pair; host_rectify.hpp compares the two.
 // One device, the whole frame (the scope of idkptDenoise): a pixel's history may lie in any row.
 #pragma once
 
@@ -50,17 +52,17 @@ static int32_t capture_records(dev_ctx* ctx, const std::string& who, int32_t slo
 static int32_t dev_CaptureGeometry(dev_ctx* ctx, int32_t slot) { return capture_records(ctx, "idkptCaptureGeometry", slot, false); }
 static int32_t dev_CaptureMotion(dev_ctx* ctx, int32_t slot) { return capture_records(ctx, "idkptCaptureMotion", slot, true); }
 
-// the record of ring slot `slot` (-1: the current one) for the calls that read one of its four images
-enum TemporalImage { TEMPORAL_IMAGE = 0, GEOMETRY_IMAGE = 1, TEMPORAL_MOMENTS_IMAGE = 2, MOTION_IMAGE = 3 };
-static bool temporal_holds(const TemporalSlot& s, TemporalImage which) { return which == GEOMETRY_IMAGE ? s.geomValid : which == TEMPORAL_IMAGE ? s.temporalValid : which == MOTION_IMAGE ? s.motionValid : s.momentsValid; }
-static const GuardedBuf& temporal_buf(const TemporalSlot& s, TemporalImage which) { return which == GEOMETRY_IMAGE ? s.geom : which == TEMPORAL_IMAGE ? s.temporal : which == MOTION_IMAGE ? s.motion : s.moments; }
+// the record of ring slot `slot` (-1: the current one) for the calls that read one of its five images
+enum TemporalImage { TEMPORAL_IMAGE = 0, GEOMETRY_IMAGE = 1, TEMPORAL_MOMENTS_IMAGE = 2, MOTION_IMAGE = 3, FAST_TEMPORAL_IMAGE = 4 };
+static bool temporal_holds(const TemporalSlot& s, TemporalImage which) { return which == GEOMETRY_IMAGE ? s.geomValid : which == TEMPORAL_IMAGE ? s.temporalValid : which == MOTION_IMAGE ? s.motionValid : which == FAST_TEMPORAL_IMAGE ? s.fastValid : s.momentsValid; }
+static const GuardedBuf& temporal_buf(const TemporalSlot& s, TemporalImage which) { return which == GEOMETRY_IMAGE ? s.geom : which == TEMPORAL_IMAGE ? s.temporal : which == MOTION_IMAGE ? s.motion : which == FAST_TEMPORAL_IMAGE ? s.fast : s.moments; }
 static int32_t temporal_slot_of(dev_ctx* ctx, const char* who, int32_t slot, TemporalImage which, TemporalSlot** out)
 {
     REQUIRE(slot >= -1 && slot < ctx->ringSize, std::string(who) + ": slot outside the frame ring (-1: the current slot)");
     if (slot < 0) slot = ctx->curSlot;
     std::vector<TemporalSlot>& v = ctx->products.temporal;
     if ((size_t)slot >= v.size() || !temporal_holds(v[slot], which))
-        return fail(ctx, IDKPT_ERR_INVALID_OPERATION, std::string(who) + (which == GEOMETRY_IMAGE ? ": the slot holds no geometry image since the last resize (idkptCaptureGeometry)" : which == TEMPORAL_IMAGE ? ": the slot holds no temporal image since the last resize (idkptReproject)" : which == MOTION_IMAGE ? ": the slot holds no motion image (idkptCaptureMotion; idkptCaptureGeometry and every resize drop it)" : ": the slot holds no temporal moments image since the last resize (idkptReprojectMoments)"));
+        return fail(ctx, IDKPT_ERR_INVALID_OPERATION, std::string(who) + (which == GEOMETRY_IMAGE ? ": the slot holds no geometry image since the last resize (idkptCaptureGeometry)" : which == TEMPORAL_IMAGE ? ": the slot holds no temporal image since the last resize (idkptReproject)" : which == MOTION_IMAGE ? ": the slot holds no motion image (idkptCaptureMotion; idkptCaptureGeometry and every resize drop it)" : which == FAST_TEMPORAL_IMAGE ? ": the slot holds no fast temporal image since the last resize (idkptReprojectFast)" : ": the slot holds no temporal moments image since the last resize (idkptReprojectMoments)"));
     *out = &v[slot];
     return IDKPT_OK;
 }
@@ -91,47 +93,56 @@ static int32_t dev_DownloadTemporalMoments(dev_ctx* ctx, int32_t slot, float* rg
 static int32_t dev_GetTemporalMomentsDevicePtr(dev_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes) { return temporal_device_ptr(ctx, "idkptGetTemporalMomentsDevicePtr", slot, TEMPORAL_MOMENTS_IMAGE, outPtr, outBytes); }
 static int32_t dev_DownloadMotion(dev_ctx* ctx, int32_t slot, float* rgba, size_t bytes) { return temporal_download(ctx, "idkptDownloadMotion", slot, MOTION_IMAGE, rgba, bytes); }
 static int32_t dev_GetMotionDevicePtr(dev_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes) { return temporal_device_ptr(ctx, "idkptGetMotionDevicePtr", slot, MOTION_IMAGE, outPtr, outBytes); }
+static int32_t dev_DownloadFastTemporal(dev_ctx* ctx, int32_t slot, float* rgba, size_t bytes) { return temporal_download(ctx, "idkptDownloadFastTemporal", slot, FAST_TEMPORAL_IMAGE, rgba, bytes); }
+static int32_t dev_GetFastTemporalDevicePtr(dev_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes) { return temporal_device_ptr(ctx, "idkptGetFastTemporalDevicePtr", slot, FAST_TEMPORAL_IMAGE, outPtr, outBytes); }
 
-static int32_t dev_Reproject(dev_ctx* ctx, int32_t slot, int32_t historySlot, const idkpt_reproject* r)
+// idkptReproject (which = TEMPORAL_IMAGE) and idkptReprojectFast (which = FAST_TEMPORAL_IMAGE): one body on the image pair (the history slot's image, the slot's image);
+// the two calls differ in the pair and in what the messages call it
+static int32_t reproject_image(dev_ctx* ctx, const std::string& who, TemporalImage which, int32_t slot, int32_t historySlot, const idkpt_reproject* r)
 {
     if (!ctx || !r) return IDKPT_ERR_INVALID_ARGUMENT;
-    REQUIRE(slot >= -1 && slot < ctx->ringSize, "idkptReproject: slot outside the frame ring (-1: the current slot)");
-    REQUIRE(historySlot == IDKPT_NO_HISTORY || (historySlot >= 0 && historySlot < ctx->ringSize), "idkptReproject: historySlot must be IDKPT_NO_HISTORY or a slot of the frame ring");
-    REQUIRE(reprojt::finite(r->PositionTolerance) && r->PositionTolerance > 0.0f, "idkptReproject: PositionTolerance must be finite and > 0");
-    REQUIRE(reprojt::finite(r->MaxHistory) && r->MaxHistory >= 1.0f, "idkptReproject: MaxHistory must be finite and >= 1");
+    const bool fast = which == FAST_TEMPORAL_IMAGE;
+    REQUIRE(slot >= -1 && slot < ctx->ringSize, who + ": slot outside the frame ring (-1: the current slot)");
+    REQUIRE(historySlot == IDKPT_NO_HISTORY || (historySlot >= 0 && historySlot < ctx->ringSize), who + ": historySlot must be IDKPT_NO_HISTORY or a slot of the frame ring");
+    REQUIRE(reprojt::finite(r->PositionTolerance) && r->PositionTolerance > 0.0f, who + ": PositionTolerance must be finite and > 0");
+    REQUIRE(reprojt::finite(r->MaxHistory) && r->MaxHistory >= 1.0f, who + ": MaxHistory must be finite and >= 1");
     if (slot < 0) slot = ctx->curSlot;
-    REQUIRE(slot != historySlot, "idkptReproject: slot and historySlot must differ (a frame is no history of itself)");
-    { int rc = denoise_scope(ctx, "idkptReproject"); if (rc) return rc; }
+    REQUIRE(slot != historySlot, who + ": slot and historySlot must differ (a frame is no history of itself)");
+    { int rc = denoise_scope(ctx, who.c_str()); if (rc) return rc; }
     std::vector<TemporalSlot>& v = ctx->products.temporal;
-    auto holds = [&](int q, bool geometry) { return (size_t)q < v.size() && (geometry ? v[q].geomValid : v[q].temporalValid); };
-    if (!holds(slot, true)) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptReproject: the slot holds no geometry image since the last resize (idkptCaptureGeometry)");
+    auto holds = [&](int q, TemporalImage im) { return (size_t)q < v.size() && temporal_holds(v[q], im); };
+    if (!holds(slot, GEOMETRY_IMAGE)) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, who + ": the slot holds no geometry image since the last resize (idkptCaptureGeometry)");
     const bool start = historySlot == IDKPT_NO_HISTORY;
-    if (!start && !holds(historySlot, true)) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptReproject: the history slot holds no geometry image since the last resize (idkptCaptureGeometry)");
-    if (!start && !holds(historySlot, false)) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptReproject: the history slot holds no temporal image since the last resize (idkptReproject)");
+    if (!start && !holds(historySlot, GEOMETRY_IMAGE)) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, who + ": the history slot holds no geometry image since the last resize (idkptCaptureGeometry)");
+    if (!start && !holds(historySlot, which)) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, who + (fast ? ": the history slot holds no fast temporal image since the last resize (idkptReprojectFast)" : ": the history slot holds no temporal image since the last resize (idkptReproject)"));
     const uint32_t n = ctx->accum[slot];                 // (queued samples included: they are launched below)
-    if (n == 0u) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, "idkptReproject: the slot has accumulated no sample");
+    if (n == 0u) return fail(ctx, IDKPT_ERR_INVALID_OPERATION, who + ": the slot has accumulated no sample");
     HIPC(hipSetDevice(ctx->device));
     FLUSH_KEEP();                                        // stream-ordered behind what was queued (as idkptDenoise)
     { int rc = check_overflow(ctx); if (rc) return rc; }   // (no wait: see idkptGetFrameDevicePtr)
     const int W = ctx->W, H = ctx->H;
     TemporalSlot& s = v[slot];
-    s.temporalValid = false;
-    HIPC(s.temporal.ensure(ctx->stream, (size_t)W * H * 16));
+    GuardedBuf& dst = fast ? s.fast : s.temporal;
+    bool& dstValid = fast ? s.fastValid : s.temporalValid;
+    dstValid = false;
+    HIPC(dst.ensure(ctx->stream, (size_t)W * H * 16));
     reprojt::Params p;
     p.W = W; p.H = H;
     memcpy(p.M, r->PrevProjView, sizeof(p.M)); memcpy(p.prevPos, r->PrevViewPos, sizeof(p.prevPos));
     p.tol2 = r->PositionTolerance * r->PositionTolerance; p.maxHistory = r->MaxHistory; p.n = (float)n;
     const dim3 grid((unsigned)((W + reprojk::TILE - 1) / reprojk::TILE), (unsigned)((H + reprojk::TILE - 1) / reprojk::TILE));
     const float4* hg = start ? nullptr : v[historySlot].geom.as<const float4>();
-    const float4* hc = start ? nullptr : v[historySlot].temporal.as<const float4>();
+    const float4* hc = start ? nullptr : temporal_buf(v[historySlot], which).as<const float4>();
     if (!start && s.motionValid)                         // the slot's surfaces are looked up where they stood in the history frame (idkptCaptureMotion)
-        hipLaunchKernelGGL(k_reproject_motion<false>, grid, dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, IDKPT_IMAGE_RESULT, slot), s.geom.as<const float4>(), s.motion.as<const float4>(), hg, hc, s.temporal.as<float4>(), p);
+        hipLaunchKernelGGL(k_reproject_motion<false>, grid, dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, IDKPT_IMAGE_RESULT, slot), s.geom.as<const float4>(), s.motion.as<const float4>(), hg, hc, dst.as<float4>(), p);
     else
-        hipLaunchKernelGGL(k_reproject, grid, dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, IDKPT_IMAGE_RESULT, slot), s.geom.as<const float4>(), hg, hc, s.temporal.as<float4>(), p);
+        hipLaunchKernelGGL(k_reproject, grid, dim3(256), 0, ctx->stream, (const float4*)image_ptr(ctx, IDKPT_IMAGE_RESULT, slot), s.geom.as<const float4>(), hg, hc, dst.as<float4>(), p);
     HIPC(hipGetLastError());
-    s.temporalValid = true;
+    dstValid = true;
     return IDKPT_OK;
 }
+static int32_t dev_Reproject(dev_ctx* ctx, int32_t slot, int32_t historySlot, const idkpt_reproject* r) { return reproject_image(ctx, "idkptReproject", TEMPORAL_IMAGE, slot, historySlot, r); }
+static int32_t dev_ReprojectFast(dev_ctx* ctx, int32_t slot, int32_t historySlot, const idkpt_reproject* r) { return reproject_image(ctx, "idkptReprojectFast", FAST_TEMPORAL_IMAGE, slot, historySlot, r); }
 
 // the luminance moments of the slot through the same taps: (m1, m2) of the moments image FinalDraw keeps (host_noise.hpp) blended with the history slot's temporal moments
 // image; independent of idkptReproject (neither reads what the other writes)

@@ -41,6 +41,7 @@ using namespace ptd;
 #include "kernels_denoise_variance.hpp"
 #include "kernels_reproject.hpp"
 #include "kernels_denoise_temporal.hpp"
+#include "kernels_rectify.hpp"
 #include "kernels_present.hpp"
 #include "bvh_gpu.hpp"
 #include "bvh_gpu_full.hpp"
@@ -62,6 +63,7 @@ using namespace ptd;
 #include "host_denoise.hpp"
 #include "host_denoise_variance.hpp"
 #include "host_reproject.hpp"
+#include "host_rectify.hpp"
 #include "host_denoise_temporal.hpp"
 #include "host_options.hpp"
 #include "transport_rccl.hpp"

@@ -964,6 +964,11 @@ int32_t idkptDenoiseTemporal(idkpt_ctx* c, int32_t slot, const idkpt_denoise_tem
 int32_t idkptCaptureMotion(idkpt_ctx* c, int32_t slot) { ONE_ONLY("idkptCaptureMotion", REPROJECT_WHY, dev_CaptureMotion(m, slot)); }
 int32_t idkptDownloadMotion(idkpt_ctx* c, int32_t slot, float* rgba, size_t bytes) { ONE_ONLY("idkptDownloadMotion", REPROJECT_WHY, dev_DownloadMotion(m, slot, rgba, bytes)); }
 int32_t idkptGetMotionDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size_t* outBytes) { ONE_ONLY("idkptGetMotionDevicePtr", REPROJECT_WHY, dev_GetMotionDevicePtr(m, slot, outPtr, outBytes)); }
+// ---- history rectification (host_reproject.hpp, host_rectify.hpp): a second, short history of the same signal, and the long one pulled towards it where they disagree
+int32_t idkptReprojectFast(idkpt_ctx* c, int32_t slot, int32_t historySlot, const idkpt_reproject* reproject) { ONE_ONLY("idkptReprojectFast", REPROJECT_WHY, dev_ReprojectFast(m, slot, historySlot, reproject)); }
+int32_t idkptDownloadFastTemporal(idkpt_ctx* c, int32_t slot, float* rgba, size_t bytes) { ONE_ONLY("idkptDownloadFastTemporal", REPROJECT_WHY, dev_DownloadFastTemporal(m, slot, rgba, bytes)); }
+int32_t idkptGetFastTemporalDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size_t* outBytes) { ONE_ONLY("idkptGetFastTemporalDevicePtr", REPROJECT_WHY, dev_GetFastTemporalDevicePtr(m, slot, outPtr, outBytes)); }
+int32_t idkptRectifyHistory(idkpt_ctx* c, int32_t slot, const idkpt_rectify* settings) { ONE_ONLY("idkptRectifyHistory", REPROJECT_WHY, dev_RectifyHistory(m, slot, settings)); }
 
 int32_t idkptResetAccumulation(idkpt_ctx* c) { if (!c) return IDKPT_ERR_INVALID_ARGUMENT; for (dev_ctx* m : c->dev) dev_ResetAccumulation(m); return IDKPT_OK; }
 int32_t idkptSetSampleSequence(idkpt_ctx* c, uint32_t first, uint32_t stride) { REPLICATE(SetSampleSequence, first, stride); }

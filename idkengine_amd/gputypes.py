@@ -254,6 +254,16 @@ class Reproject(C.Structure):
         return cls((cam.view @ cam.proj).astype(np.float32), cam.position, **kw)
 
 
+class Rectify(C.Structure):
+    """idkpt_rectify: the settings of idkptRectifyHistory (include/idkpt.h, "history rectification"; no counterpart in the reference).  Radius: the window is
+    (2 Radius + 1)^2; below ZLow standard errors of disagreement between the fast and the long history nothing happens, from ZHigh on the long history is replaced;
+    Epsilon: the absolute noise floor of the difference.  The defaults are starting values (profiles/rectify.md)."""
+    _fields_ = [("Radius", C.c_int32), ("ZLow", C.c_float), ("ZHigh", C.c_float), ("Epsilon", C.c_float)]
+
+    def __init__(self, Radius=2, ZLow=3.0, ZHigh=6.0, Epsilon=1e-3):
+        super().__init__(int(Radius), float(ZLow), float(ZHigh), float(Epsilon))
+
+
 class Stats(C.Structure):
     _fields_ = [("RaysTraced", C.c_uint64), ("PrimaryRays", C.c_uint64), ("Frames", C.c_uint64),
                 ("LastAliveCounts", C.c_uint32 * 16), ("LastTraceMs", C.c_float), ("LastFrameMs", C.c_float),

@@ -807,6 +807,39 @@ class PathTracer:
         themselves where none did); raises before the context's first CaptureMotion"""
         return self.DownloadBuffer(T.IDKPT_BUF_MOTION_PREV_POSITIONS, np.float32, int(count) * 3).reshape(-1, 3)
 
+    # ---- history rectification (idkptReprojectFast / idkptRectifyHistory): a fast history that ends lag after lighting changes; no counterpart in the reference
+    def ReprojectFast(self, slot=None, history=T.IDKPT_NO_HISTORY, settings=None):
+        """idkptReprojectFast: Reproject on the slot's FAST temporal image and the fast temporal image of ring slot `history` (settings: a gputypes.Reproject whose
+        MaxHistory is the fast cap; None: the defaults with MaxHistory = 4); history = IDKPT_NO_HISTORY starts it.  The result stays in the slot's fast temporal image
+        (DownloadFastTemporal)."""
+        if settings is None:
+            settings = T.Reproject(MaxHistory=4.0)
+        if not isinstance(settings, T.Reproject):
+            raise TypeError("ReprojectFast: settings must be a gputypes.Reproject")
+        self._check(self._L.idkptReprojectFast(self._ctx, -1 if slot is None else int(slot), int(history), C.addressof(settings)))
+
+    def DownloadFastTemporal(self, slot=None):
+        """idkptDownloadFastTemporal: (H, W, 4) float32 — rgb and the effective sample count of the fast history"""
+        out = np.zeros((self.height, self.width, 4), np.float32)
+        self._check(self._L.idkptDownloadFastTemporal(self._ctx, -1 if slot is None else int(slot), out.ctypes.data, out.nbytes))
+        return out
+
+    def fast_temporal_device_ptr(self, slot=None):
+        """idkptGetFastTemporalDevicePtr: (device pointer, bytes), valid in stream order; 64 guard bytes follow"""
+        p = C.c_void_p(); n = C.c_size_t()
+        self._check(self._L.idkptGetFastTemporalDevicePtr(self._ctx, -1 if slot is None else int(slot), C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def RectifyHistory(self, settings=None, slot=None):
+        """idkptRectifyHistory: where the slot's fast and long history disagree by more than their noise explains, its temporal image and sample count (and the count of
+        its temporal moments image) are pulled towards the fast temporal image.  Needs CaptureGeometry, Reproject and ReprojectFast of the slot.  settings: a
+        gputypes.Rectify; None = the defaults.  The temporal image moves to another buffer: ask temporal_device_ptr again afterwards."""
+        if settings is None:
+            settings = T.Rectify()
+        if not isinstance(settings, T.Rectify):
+            raise TypeError("RectifyHistory: settings must be a gputypes.Rectify")
+        self._check(self._L.idkptRectifyHistory(self._ctx, -1 if slot is None else int(slot), C.addressof(settings)))
+
     def enable_counters(self, on=True):
         self._check(self._L.idkptEnableCounters(self._ctx, 1 if on else 0))
 

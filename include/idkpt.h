@@ -868,7 +868,7 @@ IDKPT_API int32_t idkptDenoiseVariance(idkpt_ctx* ctx, int32_t slot, const idkpt
  * WHAT DETECTS CHANGE.  The position test compares WORLD positions: a tap is rejected where a different surface lies (an occlusion edge, a newly visible region) and where
  * the geometry itself moved by more than the tolerance between the two captures.  Nothing else detects a change of the scene: moved lights, changed materials and
  * geometry that moved by less than the tolerance blend into the history and fade with the cap alone, and a surface that moved ALONG itself is not followed (there are no
- * motion vectors).  A host that changes the scene in such a way starts a new history.  The geometry and the temporal image of a history slot must belong to the same frame:
+ * motion vectors).  A host that changes the scene in such a way starts a new history, or keeps a fast history beside this one ("history rectification" below).  The geometry and the temporal image of a history slot must belong to the same frame:
  * capture and reproject every frame, in this order.
  * Refusals, all checked before anything is launched — the slot's previous temporal image stays valid and untouched.  IDKPT_ERR_INVALID_ARGUMENT: a slot outside the ring
  * (-1: the current slot; historySlot takes IDKPT_NO_HISTORY or 0 .. frames - 1), slot == historySlot, a PositionTolerance that is not finite and > 0, a MaxHistory that is
@@ -1015,6 +1015,61 @@ IDKPT_API int32_t idkptDenoiseTemporal(idkpt_ctx* ctx, int32_t slot, const idkpt
 IDKPT_API int32_t idkptCaptureMotion(idkpt_ctx* ctx, int32_t slot);                                          /* centre rays of the current camera -> the slot's geometry image and motion image */
 IDKPT_API int32_t idkptDownloadMotion(idkpt_ctx* ctx, int32_t slot, float* rgba, size_t bytes);
 IDKPT_API int32_t idkptGetMotionDevicePtr(idkpt_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes);      /* stream-ordered; the guard bytes follow *outBytes */
+
+/* ---- history rectification (added under the same ABI number; detect by the symbol idkptRectifyHistory): a fast history that ends lag after lighting changes -----------
+ * THIS HAS NO COUNTERPART IN THE REFERENCE.  "WHAT DETECTS CHANGE" above names the hole: a moved light, a changed material or sky blends into the history and fades with
+ * MaxHistory alone, or the host starts a new history and is back at one sample per pixel.  The calls of this section are dual-history anti-lag: a second, SHORT history of
+ * the same signal is kept beside the long one, and where the two disagree by more than their noise explains, the long history and its sample count are pulled towards the
+ * short one.  Both histories are unbiased on an unchanged scene, so a false alarm costs variance, never bias (clamping the history to the neighbourhood's colour box has no
+ * such property and does nothing at one sample per pixel).  Everything is default-off and additive: no existing call, struct, enum value or image changes by a bit for a
+ * host that calls none of it.  Every operation of the texts below is a correctly rounded binary32 + - * / in the written order (-ffp-contract=off); fminf / fmaxf ignore a
+ * NaN operand; so the texts define the results BIT FOR BIT; they are checked against an independent numpy restatement (tests/rectify_ref.py).
+ *
+ * The fast temporal image.  A fifth image of the ring slot: RGBA32F of the render size, rgb and an effective sample count, with the temporal image's life cycle exactly:
+ * allocated at its first use, followed by 64 guard bytes of 0xA5 that nothing writes; KEPT by idkptResetAccumulation, idkptBeginFrame, idkptSetMaxBatch and
+ * idkptSetPresentationSize; released by idkptSetSize, idkptSetFrameRing with another count and every row-layout call.  idkptCaptureGeometry does not drop it.
+ *
+ * idkptReprojectFast(ctx, slot, historySlot, r) is the text of idkptReproject verbatim with two substitutions: hc = the FAST temporal image of `historySlot`, out = the
+ * FAST temporal image of `slot`.  r->MaxHistory is the fast cap: the host passes a small value (starting value 4, untuned).  IDKPT_NO_HISTORY starts it; a slot that holds
+ * a motion image is looked up through it, as idkptReproject is; arguments, refusals and scope are idkptReproject's with "fast temporal image" in the messages (the history
+ * slot needs its geometry image and its fast temporal image).  So with the same r and histories that start equal, the fast image equals the temporal image bit for bit.
+ * idkptDownloadFastTemporal (bytes = height * width * 16) and idkptGetFastTemporalDevicePtr read it as idkptDownloadTemporal / idkptGetTemporalDevicePtr do.
+ *
+ * idkptRectifyHistory(ctx, slot, s).  Inputs: t = the slot's temporal image, f = its fast temporal image, g = its geometry image.  Once per call:
+ * eps2 = Epsilon * Epsilon, lo2 = ZLow * ZLow, span = ZHigh * ZHigh - lo2.  Per pixel p, with id = the bits of g_p.w:
+ *   Window.  Taps q = p + (dx, dy), dy the outer loop over -Radius .. Radius, dx the inner one.  d_q.c = f_q.c - t_q.c for c = r, g, b.  A tap CONTRIBUTES iff it lies inside
+ *     the image, the bits of g_q.w equal id, and all three d_q.c satisfy fabsf(d) <= FLT_MAX:  cnt += 1.0f;  s1.c += d_q.c;  s2.c += d_q.c * d_q.c.
+ *   Too few taps.  If cnt < 4.0f: out = t_p.
+ *   Statistic.  Per channel: m = s1.c / cnt;  var = fmaxf(s2.c / cnt - m * m, 0.0f);  se2 = var / (cnt - 1.0f);  z2.c = (m * m) / (se2 + eps2).
+ *     z2 = fmaxf(fmaxf(z2.r, z2.g), z2.b);  lambda = fminf(fmaxf((z2 - lo2) / span, 0.0f), 1.0f).
+ *   Blend.  If !(lambda > 0), or one of the four channels of f_p or of t_p fails fabsf(c) <= FLT_MAX: out = t_p, bit for bit.  Otherwise
+ *     out.c = t_p.c + (f_p.c - t_p.c) * lambda for all FOUR channels: the effective sample count moves with the colour, so the next idkptReproject weighs the shortened
+ *     history accordingly.
+ * d is the mean disagreement of the two histories over the surface around the pixel — surface detail cancels in it, both histories see the same texture — and z2 its
+ * squared ratio to its own standard error.  Below ZLow nothing happens; from ZHigh on the long history is replaced.  No value feeds an address.
+ * Writes.  The slot's temporal image becomes `out` at every pixel, as if every read preceded every write: the kernel writes a spare image of the context (allocated at the
+ * first call, 64 guard bytes, released with the temporal images) and the two buffers are SWAPPED, so a pointer from idkptGetTemporalDevicePtr taken before the call is
+ * stale after it — ask again.  If the slot holds a temporal moments image, its .w becomes out.a at every pixel that took the blend branch and nothing else of it changes:
+ * "the moments' count equals the temporal alpha bit for bit" still holds for idkptDenoiseTemporal, which then sees fractional counts and handles them as written.
+ * (M1, M2) stay: a variance inflated by the change makes the filter blur more while the count is short.  The call is stream-ordered behind queued samples, waits for
+ * nothing and touches neither the accumulated images nor the accumulation, nor the fast temporal image, the geometry image or the motion image.
+ * Refusals, all checked before anything is launched — the previous images stay valid and untouched.  IDKPT_ERR_INVALID_ARGUMENT: a slot outside the ring (-1: the current
+ * slot), a Radius outside 1..3, a ZLow that is not finite and > 0, a ZHigh that is not finite and > ZLow, an Epsilon that is not finite and > 0, a NULL pointer.
+ * IDKPT_ERR_INVALID_OPERATION: the slot holds no geometry image, no temporal image or no fast temporal image; no size set; a multi-device context or a context that holds
+ * a shard of the rows (the scope of idkptDenoise).
+ * The per-frame order of a host: render, capture, idkptReproject, idkptReprojectMoments, idkptReprojectFast, idkptRectifyHistory, idkptDenoiseTemporal.
+ * What is not done: the scope stays one device and the whole frame; a change smaller than the per-sample noise is not detected; nothing is done for surfaces seen through
+ * a bounce (a mirror's reflection changes with the light, its id does not).  Radius, ZLow, ZHigh, Epsilon and the fast cap are starting values (profiles/rectify.md). */
+typedef struct idkpt_rectify {
+    int32_t Radius;    /* 1..3: the window is (2 Radius + 1)^2.  default 2, untuned */
+    float   ZLow;      /* > 0, finite: below it nothing happens.  default 3, untuned */
+    float   ZHigh;     /* > ZLow, finite: from it on the long history is replaced.  default 6, untuned */
+    float   Epsilon;   /* > 0, finite: the absolute noise floor of the difference.  default 1e-3, untuned */
+} idkpt_rectify;
+IDKPT_API int32_t idkptReprojectFast(idkpt_ctx* ctx, int32_t slot, int32_t historySlot, const idkpt_reproject* reproject);   /* Result and geometry of the slot, geometry and fast temporal image of the history slot -> the slot's fast temporal image */
+IDKPT_API int32_t idkptDownloadFastTemporal(idkpt_ctx* ctx, int32_t slot, float* rgba, size_t bytes);
+IDKPT_API int32_t idkptGetFastTemporalDevicePtr(idkpt_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes);   /* stream-ordered; the guard bytes follow *outBytes */
+IDKPT_API int32_t idkptRectifyHistory(idkpt_ctx* ctx, int32_t slot, const idkpt_rectify* settings);             /* temporal, fast temporal and geometry image of the slot -> its temporal image (and the count of its temporal moments) */
 
 /* ---- render ----------------------------------------------------------------------------- */
 /* PathTracer.ResetAccumulation (PathTracer.cs:334-337) */
