@@ -27,6 +27,7 @@ SYMBOLS = [
     "idkptReprojectMoments", "idkptDownloadTemporalMoments", "idkptGetTemporalMomentsDevicePtr", "idkptDenoiseTemporal",
     "idkptCaptureMotion", "idkptDownloadMotion", "idkptGetMotionDevicePtr",
     "idkptReprojectFast", "idkptDownloadFastTemporal", "idkptGetFastTemporalDevicePtr", "idkptRectifyHistory",
+    "idkptReconstructHistory",
 ]
 
 _lib = None
@@ -68,6 +69,7 @@ def load():
         "idkptDenoiseTemporal": [vp, i32, vp],
         "idkptCaptureMotion": [vp, i32], "idkptDownloadMotion": [vp, i32, vp, sz], "idkptGetMotionDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(sz)],
         "idkptReprojectFast": [vp, i32, i32, vp], "idkptDownloadFastTemporal": [vp, i32, vp, sz], "idkptGetFastTemporalDevicePtr": [vp, i32, C.POINTER(vp), C.POINTER(sz)], "idkptRectifyHistory": [vp, i32, vp],
+        "idkptReconstructHistory": [vp, i32, vp],
         "idkptRefitBlas": [vp, i32], "idkptUploadUnskinnedVertices": [vp, vp, i32], "idkptSkin": [vp, u32, u32, u32, u32],
         "idkptDownloadBuffer": [vp, i32, sz, sz, vp], "idkptResetAccumulation": [vp], "idkptSetSampleSequence": [vp, u32, u32], "idkptGetAccumulatedSamples": [vp, C.POINTER(u32)],
         "idkptRender": [vp], "idkptSynchronize": [vp], "idkptDownload": [vp, i32, vp, sz], "idkptDownloadRays": [vp, vp, sz],

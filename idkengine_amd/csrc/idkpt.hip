@@ -42,6 +42,7 @@ using namespace ptd;
 #include "kernels_reproject.hpp"
 #include "kernels_denoise_temporal.hpp"
 #include "kernels_rectify.hpp"
+#include "kernels_reconstruct.hpp"
 #include "kernels_present.hpp"
 #include "bvh_gpu.hpp"
 #include "bvh_gpu_full.hpp"
@@ -64,6 +65,7 @@ using namespace ptd;
 #include "host_denoise_variance.hpp"
 #include "host_reproject.hpp"
 #include "host_rectify.hpp"
+#include "host_reconstruct.hpp"
 #include "host_denoise_temporal.hpp"
 #include "host_options.hpp"
 #include "transport_rccl.hpp"

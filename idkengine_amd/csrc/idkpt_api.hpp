@@ -969,6 +969,8 @@ int32_t idkptReprojectFast(idkpt_ctx* c, int32_t slot, int32_t historySlot, cons
 int32_t idkptDownloadFastTemporal(idkpt_ctx* c, int32_t slot, float* rgba, size_t bytes) { ONE_ONLY("idkptDownloadFastTemporal", REPROJECT_WHY, dev_DownloadFastTemporal(m, slot, rgba, bytes)); }
 int32_t idkptGetFastTemporalDevicePtr(idkpt_ctx* c, int32_t slot, void** outPtr, size_t* outBytes) { ONE_ONLY("idkptGetFastTemporalDevicePtr", REPROJECT_WHY, dev_GetFastTemporalDevicePtr(m, slot, outPtr, outBytes)); }
 int32_t idkptRectifyHistory(idkpt_ctx* c, int32_t slot, const idkpt_rectify* settings) { ONE_ONLY("idkptRectifyHistory", REPROJECT_WHY, dev_RectifyHistory(m, slot, settings)); }
+// ---- history reconstruction (host_reconstruct.hpp): the short-history pixels of the temporal image topped up from neighbours of the same surface, in place
+int32_t idkptReconstructHistory(idkpt_ctx* c, int32_t slot, const idkpt_reconstruct* settings) { ONE_ONLY("idkptReconstructHistory", REPROJECT_WHY, dev_ReconstructHistory(m, slot, settings)); }
 
 int32_t idkptResetAccumulation(idkpt_ctx* c) { if (!c) return IDKPT_ERR_INVALID_ARGUMENT; for (dev_ctx* m : c->dev) dev_ResetAccumulation(m); return IDKPT_OK; }
 int32_t idkptSetSampleSequence(idkpt_ctx* c, uint32_t first, uint32_t stride) { REPLICATE(SetSampleSequence, first, stride); }

@@ -264,6 +264,16 @@ class Rectify(C.Structure):
         super().__init__(int(Radius), float(ZLow), float(ZHigh), float(Epsilon))
 
 
+class Reconstruct(C.Structure):
+    """idkpt_reconstruct: the settings of idkptReconstructHistory (include/idkpt.h, "history reconstruction"; no counterpart in the reference).  Taps at
+    p + Stride * (dx, dy), dx and dy in -Radius .. Radius; pixels whose temporal count is below FillBelow are topped up to it from texels of the same surface whose
+    count is at least FillBelow; AlbedoSigma / NormalSigma: the guide kernels of the filters.  The defaults are starting values (profiles/reconstruct.md)."""
+    _fields_ = [("Radius", C.c_int32), ("Stride", C.c_int32), ("FillBelow", C.c_float), ("AlbedoSigma", C.c_float), ("NormalSigma", C.c_float)]
+
+    def __init__(self, Radius=2, Stride=3, FillBelow=4.0, AlbedoSigma=0.2, NormalSigma=0.5):
+        super().__init__(int(Radius), int(Stride), float(FillBelow), float(AlbedoSigma), float(NormalSigma))
+
+
 class Stats(C.Structure):
     _fields_ = [("RaysTraced", C.c_uint64), ("PrimaryRays", C.c_uint64), ("Frames", C.c_uint64),
                 ("LastAliveCounts", C.c_uint32 * 16), ("LastTraceMs", C.c_float), ("LastFrameMs", C.c_float),

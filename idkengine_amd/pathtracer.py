@@ -840,6 +840,15 @@ class PathTracer:
             raise TypeError("RectifyHistory: settings must be a gputypes.Rectify")
         self._check(self._L.idkptRectifyHistory(self._ctx, -1 if slot is None else int(slot), C.addressof(settings)))
 
+    # ---- history reconstruction (idkptReconstructHistory): disoccluded pixels filled from their neighbours; no counterpart in the reference
+    def ReconstructHistory(self, slot=-1, **settings):
+        """idkptReconstructHistory: the pixels of the slot's temporal image whose count is below FillBelow take colour from texels of the same surface that kept their
+        history, in place (temporal_device_ptr stays valid; the counts, the temporal moments and the fast temporal image are untouched).  Needs CaptureGeometry and
+        Reproject of the slot and OutputAOVs.  Call it behind Reproject / ReprojectMoments / ReprojectFast and before RectifyHistory and DenoiseTemporal.  settings: the
+        fields of gputypes.Reconstruct (Radius, Stride, FillBelow, AlbedoSigma, NormalSigma); those not given keep their defaults."""
+        s = T.Reconstruct(**settings)
+        self._check(self._L.idkptReconstructHistory(self._ctx, int(slot), C.addressof(s)))
+
     def enable_counters(self, on=True):
         self._check(self._L.idkptEnableCounters(self._ctx, 1 if on else 0))
 

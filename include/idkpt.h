@@ -1071,6 +1071,52 @@ IDKPT_API int32_t idkptDownloadFastTemporal(idkpt_ctx* ctx, int32_t slot, float*
 IDKPT_API int32_t idkptGetFastTemporalDevicePtr(idkpt_ctx* ctx, int32_t slot, void** outPtr, size_t* outBytes);   /* stream-ordered; the guard bytes follow *outBytes */
 IDKPT_API int32_t idkptRectifyHistory(idkpt_ctx* ctx, int32_t slot, const idkpt_rectify* settings);             /* temporal, fast temporal and geometry image of the slot -> its temporal image (and the count of its temporal moments) */
 
+/* ---- history reconstruction (added under the same ABI number; detect by the symbol idkptReconstructHistory): disoccluded pixels filled from their neighbours ----------
+ * THIS HAS NO COUNTERPART IN THE REFERENCE.  Where all four taps of idkptReproject are refused — at occlusion edges, in newly visible regions, at the image border — the
+ * temporal pixel restarts at (cur.rgb, n): one sample of a path tracer without light sampling, beside pixels of the same surface that hold up to MaxHistory samples.
+ * idkptReconstructHistory is the sparse, guide-weighted gather pipelines of this family run right behind reprojection (ReLAX's "history fix"): only the short-history
+ * pixels walk taps, and they take colour from texels of the SAME surface that kept their history.  Default-off and additive: no existing call, struct, enum value or image
+ * changes by a bit for a host that does not call it.  Every operation of the text below is a correctly rounded binary32 + - * / in the written order
+ * (-ffp-contract=off); fminf ignores a NaN operand; so the text defines the result BIT FOR BIT; it is checked against an independent numpy restatement
+ * (tests/reconstruct_ref.py).
+ *
+ * idkptReconstructHistory(ctx, slot, s).  Inputs of `slot` (-1: the current slot): t = its temporal image, g = its geometry image, a, n = its accumulated Albedo and
+ * Normal images.  Once per call, in binary32: invA = 1 / (AlbedoSigma * AlbedoSigma), invN = 1 / (NormalSigma * NormalSigma), as idkptDenoiseTemporal computes them.
+ * Per pixel p = (x, y), with c = t_p.w and id = the bits of g_p.w:
+ *   1. The pixel KEEPS ITS 16 BYTES unless id != 0xFFFFFFFF (a miss is never filled), all four channels of t_p satisfy fabsf(v) <= FLT_MAX, and c < FillBelow (false
+ *      for NaN).
+ *   2. Taps q = (x + Stride * dx, y + Stride * dy), dy the outer loop over -Radius .. Radius, dx the inner one, (0, 0) skipped.  A tap is skipped when q lies outside the
+ *      image, the bits of g_q.w differ from id, a channel of t_q fails fabsf(v) <= FLT_MAX, or !(t_q.w >= FillBelow).
+ *   3. w = 1 / ((1 + dist2(a_q, a_p) * invA) * (1 + dist2(n_q, n_p) * invN)), dist2(u, v) = ((u.x - v.x)^2 + (u.y - v.y)^2) + (u.z - v.z)^2: the guide kernels of
+ *      idkptDenoiseTemporal's spatial estimate.  The tap is skipped unless w > 0 (false for a NaN weight and for the zero weight of an overflowed difference).
+ *   4. k = w * t_q.w;  S += k;  s.c += t_q.c * k for c = r, g, b: each its own running sum, in tap order.
+ *   5. If !(S > 0): the pixel keeps its bits.  Otherwise b = fminf(S, FillBelow - c), den = c + b, out.c = (t_p.c * c + (s.c / S) * b) / den for c = r, g, b, and
+ *      out.w = c, the same bits.  If a channel of out fails fabsf(v) <= FLT_MAX, the pixel keeps its bits.
+ * The gathered colour enters as b samples' worth: what the neighbours can vouch for (S, their counts under the guide weights), and never more than tops the pixel up to
+ * FillBelow.  No value feeds an address.
+ * IN PLACE.  A written texel has a count below FillBelow; a tap that contributes has a count of at least FillBelow; the count is stored with the bits it had.  So no call
+ * reads, for any result, a texel it writes, apart from the pixel's own: the kernel works in the temporal image itself, there is no spare image and no swap, the result
+ * does not depend on the execution order, and a pointer from idkptGetTemporalDevicePtr stays valid across the call.
+ * THE COUNT DOES NOT MOVE.  The temporal moments image, the fast temporal image, the geometry and motion images, Result, Albedo, Normal and the sample count are
+ * untouched, and "the moments' count equals the temporal alpha bit for bit" stays true with no moments variant.  The next idkptReproject weighs the pixel by its real
+ * count, so the borrowed colour is outweighed by real samples within a few frames: the blur is transient.
+ * Refusals, in this order, all checked before anything is launched — a refused call changes nothing.  IDKPT_ERR_INVALID_ARGUMENT: a NULL pointer, a slot outside the
+ * ring, a Radius outside 1..3, a Stride outside 1..8, a FillBelow, AlbedoSigma or NormalSigma that is not finite and > 0.  IDKPT_ERR_INVALID_OPERATION: no size set, a
+ * multi-device context or a context that holds a shard of the rows (the scope of idkptDenoise); the current settings have OutputAOVs = 0 (as the filters refuse it); the
+ * slot holds no geometry image; the slot holds no temporal image.  The call launches queued samples first, is stream-ordered and waits for nothing.
+ * The per-frame order of a host: render, capture, idkptReproject, idkptReprojectMoments, idkptReprojectFast, idkptReconstructHistory, idkptRectifyHistory,
+ * idkptDenoiseTemporal.  Reconstruction comes before rectification, so that rectification has the last word where the lighting changed.
+ * What is not done: the count is not raised and neither the moments nor the fast image is filled; one stride, no multi-scale cascade; no compaction of the short-history
+ * pixels; one device and the whole frame; nothing for surfaces seen through a bounce.  The five values are starting values (profiles/reconstruct.md). */
+typedef struct idkpt_reconstruct {
+    int32_t Radius;       /* 1, 2 or 3: taps at p + Stride * (dx, dy), dx and dy in -Radius .. Radius, without the centre.  default 2, untuned */
+    int32_t Stride;       /* 1..8 texels between taps.  default 3, untuned */
+    float   FillBelow;    /* > 0, finite: pixels whose temporal count is below it are topped up to it.  default 4, untuned */
+    float   AlbedoSigma;  /* > 0, finite: the guide kernels of the filters.  default 0.2, untuned */
+    float   NormalSigma;  /* > 0, finite.  default 0.5, untuned */
+} idkpt_reconstruct;      /* 20 bytes */
+IDKPT_API int32_t idkptReconstructHistory(idkpt_ctx* ctx, int32_t slot, const idkpt_reconstruct* settings);      /* temporal, geometry, Albedo and Normal image of the slot -> the rgb of its short-history temporal pixels, in place */
+
 /* ---- render ----------------------------------------------------------------------------- */
 /* PathTracer.ResetAccumulation (PathTracer.cs:334-337) */
 IDKPT_API int32_t idkptResetAccumulation(idkpt_ctx* ctx);
